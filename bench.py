@@ -1,8 +1,14 @@
 #!/usr/bin/env python
 """bench.py — R2L W256D88 ray throughput at 800x800 on N MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's frames if --dump-outputs is given and prints
+the line: headline, per-step device times, the roofline of the timed launches, the calibration and range watch.  --full adds
+what takes work of its own after the timed steps: CPU baseline and parity against the CPU oracle, the fp16x3 rate, the rungs of
+`--precision auto` (headline weights, e4m3 and stress weights), the teacher, the trained-like fixture, the create_data leg and,
+at N > 1, the check of the assembled frames.
 
 N > 1 without a torchrun environment (WORLD_SIZE unset): this process starts the N ranks itself -- fresh child processes of
 this script, before anything here imports torch or touches the GPU (efficient-nerf_amd/launch.py) -- relays rank 0's JSON
@@ -15,7 +21,7 @@ frames on every rank (weak scaling: 640,000 rays per GPU per step).  Inputs
 (weights, poses) are resident in HBM before the timed region.  The timed region is
 bracketed by barrier + synchronize on both sides, max over ranks; rank 0 prints one JSON
 line.  `roofline` is measured live with HIP events around the dominant kernel on its
-launch stream; `cpu_baseline` times the CPU oracle on this box's host cores (rank 0, N=1).
+launch stream; `cpu_baseline` (--full) times the CPU oracle on this box's host cores (rank 0, N=1).
 """
 import argparse
 import json
@@ -347,6 +353,24 @@ def middle_rung(torch, O, R2LEngine, sd, poses, focal):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(d, frames):
+    """--dump-outputs: what a caller of the timed path (render_batch + gather_rows) receives from its last step, the assembled
+    frames [F, H*W, 3] f32, as d/rgb.npy [F, H, W, 3].  Inputs are seeded, so two builds can be compared output for output.
+    Past 64 MB (F > 8) d/rgb_sample.npy instead: a fixed, seeded sample of 4,194,304 rays over all frames, [n, 3] (48 MB)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    a = frames.detach().cpu().numpy().astype(np.float32, copy=False)
+    if a.nbytes <= DUMP_MAX_BYTES:
+        np.save(os.path.join(d, 'rgb.npy'), a.reshape(a.shape[0], H, W, 3))
+        return
+    flat = a.reshape(-1, 3)
+    idx = np.sort(np.random.default_rng(0).choice(flat.shape[0], DUMP_MAX_BYTES // 16, replace=False))
+    np.save(os.path.join(d, 'rgb_sample.npy'), flat[idx])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -369,6 +393,12 @@ def main():
                     help='rays of one frame the CPU oracle renders for the baseline / parity check')
     ap.add_argument('--launch-timeout', type=float, default=1500.,
                     help='N > 1 started without torchrun: seconds after which the launcher stops its ranks and exits 124')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also run the secondary measurements and checks (CPU baseline and parity, fp16x3 rate, '
+                         'auto / e4m3 / stress rungs, teacher, trained-like fixture, create_data, N > 1 gather check); the --no-* '
+                         'flags above switch single legs of it off')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the frames the last timed step computed to DIR/rgb.npy (float32 [frames, H, W, 3])')
     args = ap.parse_args()
 
     launch = load_launcher()
@@ -445,6 +475,9 @@ def main():
     step_ms = sorted(ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps))
     kern_ms, n_launch = eng.kernel_time_ms(reset=True)
     eng.timing(False)
+    if args.dump_outputs and rank == 0:
+        # before anything below renders into the buffers the last step's frames are in
+        dump_outputs(args.dump_outputs, frames)
     if world > 1:
         import torch.distributed as dist
         t = torch.tensor([dt], dtype=torch.float64, device=dev if dist.get_backend() == 'nccl' else 'cpu')
@@ -514,7 +547,7 @@ def main():
                                   # part of the 1.75x headroom at no loss); within_limit: no fill passed check_ranges' 0.9, nothing clamped
                                   within_limit=bool(not st['saturated'] and max(st['h0_fill'], st['worst_fill']) <= eng.FILL_LIMIT))
 
-    if world > 1:
+    if world > 1 and args.full:
         # the assembled frames of the last step against this rank's own render of all rows of the step's first frame: a
         # ray's result does not depend on the launch it is in, so the collective's output must match bit for bit
         last = total_steps - 1
@@ -526,7 +559,7 @@ def main():
         out['gather_check'] = {'assembled_frame_equals_own_render_on_every_rank': bool(flag.item() == 1),
                                'collective': D.gather_backend(dev.index, world), 'fallback_allowed': bool(args.allow_fallback)}
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # parity on the bounded CPU sample + CPU baseline (same box, same run)
         n_cpu_rows = max(1, min(H, args.cpu_rays // W))
         c2w = poses[0]
@@ -678,6 +711,7 @@ def main():
                 out['trained_like'] = tl
         if not args.no_create_data and world == 1:
             out['create_data'] = create_data_leg(torch, O, args.precision if args.precision in ('fp16x3', 'fp16x1') else 'auto')
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         import torch.distributed as dist

@@ -1,5 +1,5 @@
 """GPU: bench.py prints exactly one JSON line carrying the driver's contract fields, the roofline
-and (at N = 1) the CPU baseline + parity objects."""
+and (at N = 1, with --full) the CPU baseline + parity objects; without --full only the timed steps."""
 import json
 import os
 import subprocess
@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_line_schema():
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
-                        '--cpu-rays', '8000', '--no-teacher', '--no-trained-like'], cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        '--cpu-rays', '8000', '--no-teacher', '--no-trained-like', '--full'], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -66,7 +66,7 @@ def test_bench_line_round4_fields():
     """the config-5 leg at the reference's own group size, where the traffic figure comes from,
     and for which activations the headline rate holds"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '2', '--warmup', '1',
-                        '--no-cpu-baseline', '--no-teacher'], cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        '--no-cpu-baseline', '--no-teacher', '--full'], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
     assert 'traffic_source' in d['roofline'] and isinstance(d['roofline']['traffic_source'], str)
@@ -103,11 +103,43 @@ def test_bench_line_round4_fields():
     assert 'value_valid_for' in d and 'trained-like' in d['value_valid_for']
 
 
+def test_plain_run_times_its_steps_only_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline of the timed steps and nothing that takes work of its own; --dump-outputs
+    writes the frame of the last timed step (pose 3 at --steps 3 --warmup 1), which matches the CPU oracle and is the same
+    from run to run"""
+    import numpy as np
+    import torch
+    from oracle import r2l_oracle as O
+
+    def run(d):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                            '--dump-outputs', str(d)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        return json.loads(lines[0]), np.load(os.path.join(str(d), 'rgb.npy'))
+
+    d, rgb = run(tmp_path / 'a')
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['unit'] == 'rays/s' and d['higher_is_better'] is True
+    assert abs(d['value'] - 640000 * 1e3 / d['ms_per_step']) <= 1e-6 * d['value'] and d['range_watch']['launches'] == 3
+    for k in ('cpu_baseline', 'parity', 'alt_precision', 'auto_on_these_weights', 'e4m3_mode', 'stress_weights', 'teacher',
+              'trained_like', 'create_data', 'gather_check'):
+        assert k not in d, k
+    assert rgb.dtype == np.float32 and rgb.shape == (1, 800, 800, 3) and np.isfinite(rgb).all()
+    sd = O.make_r2l_state(seed=0)
+    c2w = O.novel_poses(200)[3][:3, :4]
+    want = O.r2l_render(sd, 800, 800, O.focal_from_angle(800), c2w, rows=(0, 800, 100), chunk=16384)
+    got = torch.from_numpy(rgb[0, ::100].reshape(-1, 3).copy())
+    assert (got - want).abs().max().item() <= 1e-4
+    _, rgb2 = run(tmp_path / 'b')
+    assert np.array_equal(rgb, rgb2)
+
+
 def _torchrun_bench(extra, port):
     env = dict(os.environ, R2L_DIST_BACKEND='gloo')
     return subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr',
                            '127.0.0.1', '--master-port', str(port), os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2',
-                           '--warmup', '1', '--no-cpu-baseline', '--no-teacher', '--no-trained-like'] + extra, cwd=ROOT, env=env, capture_output=True,
+                           '--warmup', '1', '--no-cpu-baseline', '--no-teacher', '--no-trained-like', '--full'] + extra, cwd=ROOT, env=env, capture_output=True,
                           text=True, timeout=900)
 
 
@@ -141,7 +173,8 @@ def _self_launched_bench(extra):
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'LOCAL_WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT'):
         env.pop(k, None)
     return subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1',
-                           '--no-cpu-baseline', '--no-teacher', '--no-create-data', '--no-trained-like', '--launch-timeout', '800'] + extra, cwd=ROOT,
+                           '--no-cpu-baseline', '--no-teacher', '--no-create-data', '--no-trained-like', '--launch-timeout', '800', '--full'] + extra,
+                          cwd=ROOT,
                           env=env, capture_output=True, text=True, timeout=900)
 
 

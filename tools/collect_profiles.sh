@@ -11,10 +11,10 @@ cd /tmp && export TMPDIR=/tmp
 # (one gpurun call each: the whole set exceeds a call's 20 minutes since bench.py carries the create_data leg)
 PART=${PART:-AB}
 if [[ $PART == *A* ]]; then
-python $R/bench.py > $O/bench_n1_fp16_fp8.json 2> $O/bench.err || exit 1
-python $R/bench.py --precision fp16x3 --no-cpu-baseline --no-teacher --no-trained-like > $O/bench_n1_fp16x3.json 2>> $O/bench.err || exit 1
-python $R/bench.py --precision fp16_e4m3 --no-teacher --no-trained-like > $O/bench_n1_fp16_e4m3.json 2>> $O/bench.err || exit 1
-python $R/bench.py --precision fp16x3_asm --no-teacher --no-trained-like > $O/bench_n1_fp16x3_asm.json 2>> $O/bench.err || exit 1
+python $R/bench.py --full > $O/bench_n1_fp16_fp8.json 2> $O/bench.err || exit 1
+python $R/bench.py --full --precision fp16x3 --no-cpu-baseline --no-teacher --no-trained-like > $O/bench_n1_fp16x3.json 2>> $O/bench.err || exit 1
+python $R/bench.py --full --precision fp16_e4m3 --no-teacher --no-trained-like > $O/bench_n1_fp16_e4m3.json 2>> $O/bench.err || exit 1
+python $R/bench.py --full --precision fp16x3_asm --no-teacher --no-trained-like > $O/bench_n1_fp16x3_asm.json 2>> $O/bench.err || exit 1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python $R/bench.py --no-cpu-baseline --no-teacher --no-create-data --no-trained-like > $O/trace.log 2>&1 || exit 1
 for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_WAIT_INST_LDS" \
            "GRBM_GUI_ACTIVE SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_VMEM SQ_LDS_BANK_CONFLICT SQ_INSTS_VALU_MFMA_MOPS_F16" \
@@ -27,7 +27,7 @@ for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE
 done
 # round 6: the kernel trace of the TRAINED-LIKE legs (student on its split rung: r2l_head_kernel<true>, r2l_bodyx_kernel,
 # r2l_body8_kernel; teacher: coarse nerf_chain_kernel<false, 2, true>, fine nerf_chain_kernel<false, 2, false, true>), the program directly after `--`
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_trained -- python $R/bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-teacher --no-create-data > $O/trace_trained.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_trained -- python $R/bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-teacher --no-create-data > $O/trace_trained.log 2>&1 || exit 1
 python $R/tools/traffic_json.py $O/pmc_FETCH_SIZE/*/*counter_collection.csv $O/pmc_WRITE_SIZE/*/*counter_collection.csv r2l_body_kernel fp16_fp8 $O/traffic.json
 cat $O/bench_n1_fp16_fp8.json
 fi

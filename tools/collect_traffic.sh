@@ -14,5 +14,5 @@ for set in "FETCH_SIZE" "WRITE_SIZE"; do
   python $R/tools/pmc_summary.py $O/pmc_$set/*/*counter_collection.csv 'r2l_head' >> $O/pmc_$set.txt 2>&1
 done
 python $R/tools/traffic_json.py $O/pmc_FETCH_SIZE/*/*counter_collection.csv $O/pmc_WRITE_SIZE/*/*counter_collection.csv r2l_body fp16_fp8 $O/traffic.json
-python $R/bench.py > $O/bench_n1_fp16_fp8.json 2> $O/bench.err
+python $R/bench.py --full > $O/bench_n1_fp16_fp8.json 2> $O/bench.err
 cat $O/traffic.json

@@ -6,7 +6,7 @@ R=${1:-r06}
 OUT=gpurun_out/${R}_launcher_rehearsal.txt
 mkdir -p gpurun_out
 export R2L_DIST_BACKEND=gloo
-FLAGS="--steps 4 --warmup 2 --no-cpu-baseline --no-teacher --no-create-data --no-trained-like --allow-fallback"
+FLAGS="--full --steps 4 --warmup 2 --no-cpu-baseline --no-teacher --no-create-data --no-trained-like --allow-fallback"
 : > $OUT
 for N in 2 6; do
   timeout -k 10 300 python bench.py --gpus $N $FLAGS > gpurun_out/reh_$N.json 2> gpurun_out/reh_$N.err
