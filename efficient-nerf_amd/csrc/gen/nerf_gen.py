@@ -32,6 +32,7 @@ kernel prologue) and ends with the next tile's chunks 0..2 in flight.
 runs the lane-accurate emulator against a float64 evaluation of the network and the static hazard check of isa.py.
 """
 import argparse
+import collections
 import os
 import sys
 
@@ -41,6 +42,38 @@ import isa as B
 from isa import (Ins, vr, ar, vreg, areg, sreg, waitcnt_lgkm, waitcnt_vm, barrier, valu, v_max0, v_accw, v_accr, v_cvt_pk_f16,
                  v_cvt_pk32_bf6, s_nop, salu, ds_read_b128, ds_read_b64, f_to_bf6, pack6, layer_exponent, weight_exps,
                  f32_bits, Filler, check_hazards_stream, kappa16 as kappa, mix16 as mix_feat)
+
+# ---------------------------------------------------------------------------------------------
+# the variants of the chain: the ONLY place this generator names them (NERF_GEN_FMT selects a row; the comments at FMT below say what
+# each one is for).  csrc/Makefile lists the same suffix:variant pairs, csrc/nerf_common.h holds the C++ side of the `fmt` column
+# (NerfChainFmt / kNerfChain); tests/test_nerf_genx_cpu.py compares the three.
+#   base    arithmetic of the 256-wide layers: bf6 (fp16 + two bf6 terms) | f16 (one fp16 pass) | f16p3 (three fp16 passes) | mix
+#   nc      column tiles of 16 points per wave          alpha   no view branch: trunk + the alpha row
+#   skipv   second exit behind the density              emb     ONE statement: tile loop, ray loads, embedding and raw stores in the stream
+#   suffix  nerf_mlp<suffix>_*.inc                      fmt     stream format the C++ packer is asked for (nerf_debug_pack_chain_host)
+#   mode, kernel: the precision mode that launches it and the instantiation that includes its text (csrc/nerf_kernels.hip)
+# ---------------------------------------------------------------------------------------------
+Variant = collections.namedtuple('Variant', 'base nc alpha skipv emb suffix fmt mode kernel')
+VARIANTS = {
+    'bf6':    Variant('bf6',   2, False, False, False, '',    0, 'R2L_PREC_FP16_FP8',   'nerf_chain_kernel<false, 2>'),
+    'f16':    Variant('f16',   2, False, False, False, 'x',   1, 'R2L_PREC_FP16X1',     'nerf_chain_kernel<true, 2>'),
+    'f16c3':  Variant('f16',   3, False, False, False, 'x3',  1, 'R2L_PREC_FP16X1',     'nerf_chain_kernel<true, 3>'),
+    'f16c4':  Variant('f16',   4, False, False, False, 'x4',  1, 'R2L_PREC_FP16X1',     'nerf_chain_kernel<true, 4>'),
+    'f16c4e': Variant('f16',   4, False, False, True,  'x4e', 1, 'R2L_PREC_FP16X1',     'nerf_chain_emb_kernel'),
+    'f16p3':  Variant('f16p3', 2, False, False, False, 'p3',  2, 'R2L_PREC_FP16X3_ASM', 'nerf_chain_kernel<false, 2, true>'),
+    'mix':    Variant('mix',   2, False, False, False, 'm',   3, 'R2L_PREC_FP16_MIX',   'nerf_chain_kernel<false, 2, false, true>'),
+    'f16p3a': Variant('f16p3', 2, True,  False, False, 'p3a', 4, 'R2L_PREC_FP16X3_ASM', 'nerf_chain_kernel<false, 2, true, false, true>'),
+    'f16p3s': Variant('f16p3', 2, False, True,  False, 'p3s', 5, 'R2L_PREC_FP16X3_ASM', 'nerf_chain_kernel<false, 2, true, false, false, true>'),
+    'mixs':   Variant('mix',   2, False, True,  False, 'ms',  6, 'R2L_PREC_FP16_MIX',   'nerf_chain_kernel<false, 2, false, true, false, true>'),
+}
+
+
+def inc_files(name):
+    """the files variant `name` emits: the tile block and its clobber list, then (unless the statement holds the whole kernel) the ring
+    prologue and its clobber list"""
+    v = VARIANTS[name]
+    return ['nerf_mlp%s%s.inc' % (v.suffix, k) for k in (('_asm', '_clobbers') if v.emb else ('_asm', '_pro_asm', '_clobbers', '_pro_clobbers'))]
+
 
 # ---------------------------------------------------------------------------------------------
 # register map
@@ -87,8 +120,10 @@ ACT_EXP, RES_EXP = B.ACT_EXP, B.RES_EXP
 # of set P and from there into its AGPRs behind the V layer's last embedding k-step), and raw is stored by the stream: the HIP prologue
 # that computed the embedding between two blocks while the matrix pipe idled (2.3 ms of a 33.4 ms frame, -DNERF_SKIP_EMBED) is gone.
 # The arithmetic per point is that of nerf_tile_embed (csrc/nerf_kernels.hip), operation for operation: bitwise-equal results.
-FMT = os.environ.get('NERF_GEN_FMT', 'bf6')
-assert FMT in ('bf6', 'f16', 'f16c3', 'f16c4', 'f16c4e', 'f16p3', 'f16p3a', 'f16p3s', 'mix', 'mixs'), FMT
+VARIANT = os.environ.get('NERF_GEN_FMT', 'bf6')
+assert VARIANT in VARIANTS, VARIANT
+_V = VARIANTS[VARIANT]
+FMT = _V.base
 # NERF_GEN_FMT=mix (round 6): the bf6 chain with its FIRST trunk layers in three fp16 passes -- layers L1 .. L<MIXK> as in f16p3 (hi / lo
 # fragments of both operands, W x 2^k in the stream), everything behind them with bf6 terms.  For the FINE pass of trained teachers: the
 # early layers' error is what the sharp tail of such a network amplifies (tools/teacher_mixed_study.py on whole frames of the trained-like
@@ -102,9 +137,7 @@ assert FMT in ('bf6', 'f16', 'f16c3', 'f16c4', 'f16c4e', 'f16p3', 'f16p3a', 'f16
 # fine pass depend on the coarse network through its densities only (main.py:716-733), and the reference's call sites drop rgb0
 # (main.py:277-282, utils/create_data.py:824-831: `rgb, disp, acc, _ = render(...)`).  17 % of the network's MACs; the alpha row gets its
 # own weight scale 2^k.  A second, all-zero row tile keeps the chunk count a multiple of the ring's four slots (68).
-ALPHA = FMT == 'f16p3a'
-if ALPHA:
-    FMT = 'f16p3'
+ALPHA = _V.alpha
 # NERF_GEN_FMT=f16p3s / mixs (round 6): the chain with a SECOND EXIT behind the density.  A sample whose raw density is <= 0 has alpha = 0 and
 # weight 0 exactly (main.py:600-606): its colour cannot reach rgb_map.  The feature | alpha layer is split -- layer A: the alpha row alone,
 # FIRST; layer F: the 256 feature rows -- and behind A's epilogue the four waves of the workgroup agree (an OR through an LDS word, one
@@ -112,15 +145,14 @@ if ALPHA:
 # work -- the block waits for the LDS-DMA pieces in flight, re-primes the ring with the next tile's first three chunks and leaves with
 # raw = (0, 0, 0, sigma).  rgb / disp / acc / depth are bit for bit what the full chain gives (0 x sigmoid(c) = 0 either way); `raw` shows
 # zeros for the colours of such tiles.  For renders whose caller drops the extras (nerf_set_skip_rgb0) and adds no density noise.
-SKIPV = FMT in ('f16p3s', 'mixs')
+SKIPV = _V.skipv
 if SKIPV:
-    FMT = FMT[:-1]
     N_SGPR_HI = 60
 MIX = FMT == 'mix'
 MIXK = int(os.environ.get('NERF_GEN_MIX_K', '2')) if MIX else 0
 assert 0 <= MIXK <= 7
 X1 = FMT not in ('bf6', 'mix')
-EMB = FMT == 'f16c4e'
+EMB = _V.emb
 # NERF_GEN_FMT=f16p3 (round 5): fp16x3's arithmetic on the generated chain -- per k-step three fp16 MFMAs on one accumulate chain,
 # hi(W) hi(a) + hi(W) lo(a) + lo(W) hi(a), lo = the fp16 rounding residual -- for teachers that need fp32-grade arithmetic: every
 # TRAINED one (profiles/r05_trained_like.txt: sharp densities amplify a single pass's 1e-5 to 3e-3, and the fine samples follow the
@@ -128,8 +160,8 @@ EMB = FMT == 'f16c4e'
 # lo(a) a second pair of activation sets in AGPRs; the stream holds W x 2^k (k per layer: max|w| 2^k in [2^12, 2^13)) so that lo(W) is
 # a normal fp16 number, the epilogue takes the factor out (one v_fma_mix per value does it together with the conversion to fp16).
 P3 = FMT == 'f16p3'
-NC = {'f16c3': 3, 'f16c4': 4, 'f16c4e': 4}.get(FMT, 2)          # column tiles (16 points each) per wave
-SUFFIX = {'bf6': '', 'f16': 'x', 'f16c3': 'x3', 'f16c4': 'x4', 'f16c4e': 'x4e', 'f16p3': 'p3', 'mix': 'm'}[FMT] + ('a' if ALPHA else '') + ('s' if SKIPV else '')     # nerf_mlpx_asm.inc ...
+NC = _V.nc                     # column tiles (16 points each) per wave
+SUFFIX = _V.suffix             # nerf_mlpx_asm.inc ...
 # passes of an embedding k-step: hi(W) hi(E), hi(W) lo(E), lo(W) hi(E).  The fp16-only chains drop the third (their 256-wide layers
 # carry no lo(W) term either; measured over whole frames, three seed pairs x three poses: rgb 6.5e-6 .. 1.9e-5 from fp16x3 with two
 # passes against 6.4e-6 .. 1.6e-5 with three, -4.4 % time; ONE pass -- no lo(E), i.e. fp16-rounded coordinates -- reads 1.3 .. 2.8e-5
@@ -1720,14 +1752,15 @@ def emit_kernel(dirname, opts):
     n = {}
     for ins in body:
         n[ins.kind] = n.get(ins.kind, 0) + 1
-    with open(os.path.join(dirname, 'nerf_mlp%s_asm.inc' % SUFFIX), 'w') as f:
+    f_asm, f_clob = [os.path.join(dirname, x) for x in inc_files(VARIANT)]
+    with open(f_asm, 'w') as f:
         f.write('// GENERATED by gen/nerf_gen.py (NERF_GEN_FMT=%s) -- do not edit.  The fp16-only teacher chain as one statement: ring prologue, first '
                 "tile's embedding, tile loop (ray loads, eleven layers, the next tile's embedding as fillers, raw stores).  Per tile: %s\n" %
-                (FMT, ', '.join('%s %d' % kv for kv in sorted(n.items()))))
+                (VARIANT, ', '.join('%s %d' % kv for kv in sorted(n.items()))))
         for line in lines:
             f.write('"%s\\n\\t"\n' % line)
     regs = ['v%d' % i for i in range(256)] + ['a%d' % i for i in range(256)] + ['s%d' % i for i in range(N_SGPR_LO, N_SGPR_HI)] + ['vcc', 'scc', 'memory']
-    with open(os.path.join(dirname, 'nerf_mlp%s_clobbers.inc' % SUFFIX), 'w') as f:
+    with open(f_clob, 'w') as f:
         f.write('// GENERATED by gen/nerf_gen.py: registers the kernel statement owns\n' + ', '.join('"%s"' % r for r in regs) + '\n')
     return n, body
 
@@ -1780,7 +1813,8 @@ def emit(dirname, opts):
     n = {}
     for ins in body:
         n[ins.kind] = n.get(ins.kind, 0) + 1
-    with open(os.path.join(dirname, 'nerf_mlp%s_asm.inc' % SUFFIX), 'w') as f:
+    f_asm, f_pro, f_clob, f_pro_clob = [os.path.join(dirname, x) for x in inc_files(VARIANT)]
+    with open(f_asm, 'w') as f:
         f.write('// GENERATED by gen/nerf_gen.py -- do not edit.  One 128-point tile of the teacher MLP: %s\n' %
                 ', '.join('%s %d' % kv for kv in sorted(n.items())))
         lines = setup + [i.text for i in body]
@@ -1788,7 +1822,7 @@ def emit(dirname, opts):
             lines += ['s_branch L_done_%=', 'L_skip_%=:'] + [i.text for i in skip_tail_ops()] + ['L_done_%=:']
         for line in lines + ['s_mov_b32 m0, %s' % sreg(S_M0SAVE)]:
             f.write('"%s\\n\\t"\n' % line)
-    with open(os.path.join(dirname, 'nerf_mlp%s_pro_asm.inc' % SUFFIX), 'w') as f:
+    with open(f_pro, 'w') as f:
         f.write('// GENERATED by gen/nerf_gen.py -- do not edit.  Ring prologue: chunks 0..2 of the stream\n')
         for line in setup + [i.text for i in prologue_ops()] + ['s_mov_b32 m0, %s' % sreg(S_M0SAVE)]:
             f.write('"%s\\n\\t"\n' % line)
@@ -1799,9 +1833,9 @@ def emit(dirname, opts):
         regs += ['s%d' % i for i in range(N_SGPR_LO, N_SGPR_HI)] + ['vcc', 'scc', 'memory']
         return ', '.join('"%s"' % r for r in regs) + '\n'
 
-    with open(os.path.join(dirname, 'nerf_mlp%s_clobbers.inc' % SUFFIX), 'w') as f:
+    with open(f_clob, 'w') as f:
         f.write('// GENERATED by gen/nerf_gen.py: registers the tile block owns\n' + clob(0, N_VGPR_CLOBBER, N_AGPR_CLOBBER))
-    with open(os.path.join(dirname, 'nerf_mlp%s_pro_clobbers.inc' % SUFFIX), 'w') as f:
+    with open(f_pro_clob, 'w') as f:
         f.write('// GENERATED by gen/nerf_gen.py: registers the ring prologue owns\n' + clob(V_L0, N_VGPR_CLOBBER, 0))
     return n, body
 
@@ -1860,7 +1894,7 @@ def main():
     a = ap.parse_args()
     given = {k: v for k, v in dict(lead=a.lead, lead6=a.lead6, cap=a.cap, dma_gap=a.dma_gap, wait_group=a.wait_group).items() if v is not None}
     opts = Opts(pair=a.pair, drop=tuple(x for x in a.drop.split(',') if x), **given)
-    print('format', FMT, 'tiles', NT, 'chunks', NCH, 'MFMAs', N_ANCH, 'stream bytes', STREAM_BYTES)
+    print('format', VARIANT, 'tiles', NT, 'chunks', NCH, 'MFMAs', N_ANCH, 'stream bytes', STREAM_BYTES)
     if a.emit:
         n, body = (emit_kernel if EMB else emit)(a.emit, opts)
         print('wrote', a.emit, n, 'model cycles per tile', model_cycles(body))

@@ -93,30 +93,61 @@ float max_scale(std::initializer_list<std::pair<const float*, size_t>> ts) {
 // bf6 operands as in the R2L body (r2l_capi.hip): term 0 = (w - hi(w)) / 2^(e-16), term 1 = w / 2^(e-4), e = exponent
 // of the layer's max|w|, element i of a lane = input feature r2l_mix_feat(t, lane>>4, i).  Behind the stream: the
 // resident table, per layer NERF_CHAIN_AUX_LAYER bytes = bias x act_scale | the two E8M0 scale bytes per lane quarter.
-struct ChainLayer { int ks, nx, rt, rpc, fan_out; };
-const ChainLayer kChain[11] = {{0, 2, 16, 8, 256}, {8, 0, 16, 2, 256}, {8, 0, 16, 2, 256}, {8, 0, 16, 2, 256},
-                               {8, 0, 16, 2, 256}, {8, 2, 16, 1, 256}, {8, 0, 16, 2, 256}, {8, 0, 16, 2, 256},
-                               {8, 0, 17, 2, 257}, {8, 1, 8, 2, 128},  {4, 0, 1, 1, 3}};
-// FP16X1 (no bf6 operands): twice the row tiles per chunk where a 32 KiB ring slot allows -- 44 chunks per tile instead of 80
-const ChainLayer kChainX[11] = {{0, 2, 16, 8, 256}, {8, 0, 16, 4, 256}, {8, 0, 16, 4, 256}, {8, 0, 16, 4, 256},
-                                {8, 0, 16, 4, 256}, {8, 2, 16, 2, 256}, {8, 0, 16, 4, 256}, {8, 0, 16, 4, 256},
-                                {8, 0, 17, 4, 257}, {8, 1, 8, 2, 128},  {4, 0, 1, 1, 3}};
-// FP16X3_ASM (gen/nerf_gen.py NERF_GEN_FMT=f16p3): per main k-step a hi AND a lo fragment of W x 2^k -- 84 chunks of <= 32 KiB
-const ChainLayer kChainP3[11] = {{0, 2, 16, 8, 256}, {8, 0, 16, 2, 256}, {8, 0, 16, 2, 256}, {8, 0, 16, 2, 256},
-                                 {8, 0, 16, 2, 256}, {8, 2, 16, 1, 256}, {8, 0, 16, 2, 256}, {8, 0, 16, 2, 256},
-                                 {8, 0, 17, 2, 257}, {8, 1, 8, 1, 128},  {4, 0, 1, 1, 3}};
-
-// FP16X3_ASM without the view branch (NERF_GEN_FMT=f16p3a): the trunk of kChainP3, then the alpha row alone (row tile 0; row tile 1 is
-// padding: 68 chunks = 0 mod 4) -- for the coarse pass of renders whose caller does not take rgb0 (nerf_set_skip_rgb0)
-const ChainLayer kChainP3A[9] = {{0, 2, 16, 8, 256}, {8, 0, 16, 2, 256}, {8, 0, 16, 2, 256}, {8, 0, 16, 2, 256},
-                                 {8, 0, 16, 2, 256}, {8, 2, 16, 1, 256}, {8, 0, 16, 2, 256}, {8, 0, 16, 2, 256}, {8, 0, 2, 1, 1}};
-
-// the chains with a second exit behind the density (NERF_GEN_FMT=f16p3s / mixs): layer 8 = the alpha row (one row tile, one chunk), layer 9 =
-// the 256 feature rows, then views and rgb: 12 layers
-const ChainLayer kChainP3S[12] = {{0, 2, 16, 8, 256}, {8, 0, 16, 2, 256}, {8, 0, 16, 2, 256}, {8, 0, 16, 2, 256}, {8, 0, 16, 2, 256}, {8, 2, 16, 1, 256},
-                                  {8, 0, 16, 2, 256}, {8, 0, 16, 2, 256}, {8, 0, 1, 1, 1},   {8, 0, 16, 2, 256}, {8, 1, 8, 1, 128},  {4, 0, 1, 1, 3}};
-const ChainLayer kChainS[12] = {{0, 2, 16, 8, 256}, {8, 0, 16, 2, 256}, {8, 0, 16, 2, 256}, {8, 0, 16, 2, 256}, {8, 0, 16, 2, 256}, {8, 2, 16, 1, 256},
-                                {8, 0, 16, 2, 256}, {8, 0, 16, 2, 256}, {8, 0, 1, 1, 1},   {8, 0, 16, 2, 256}, {8, 1, 8, 2, 128},  {4, 0, 1, 1, 3}};
+struct ChainLayer {
+    int ks, nx, rt, rpc, fan_out;
+    bool p3;    // main k-steps as three fp16 passes: per row tile KS hi fragments, then KS lo fragments, of W x 2^k; no bf6 operands
+    int nj;     // bf6 operands per row tile
+};
+struct Chain { ChainLayer l[12]; int n; };
+// The layers of a stream format, from its flags, as chain() of gen/nerf_gen.py builds them.  Row tiles per chunk (a chunk must fit a
+// 32 KiB ring slot) of the standard layers, L5 and V: three passes 2, 1, 1; fp16 only 4, 2, 2 (44 chunks per tile instead of 80); bf6 2, 1, 2.
+constexpr Chain chain_layers(const NerfChainDesc& d) {
+    const int r_std = d.all_p3 ? 2 : d.x1 ? 4 : 2, r_l5 = d.all_p3 ? 1 : d.x1 ? 2 : 1, r_v = d.all_p3 ? 1 : 2;
+    const ChainLayer std_layer = {8, 0, 16, r_std, 256};
+    Chain c = {};
+    c.l[c.n++] = {0, 2, 16, 8, 256};                             // L0: the pts embedding's two k-steps
+    for (int i = 1; i <= 4; ++i) c.l[c.n++] = std_layer;
+    c.l[c.n++] = {8, 2, 16, r_l5, 256};                          // L5: cat([input_pts, h])
+    c.l[c.n++] = std_layer;
+    c.l[c.n++] = std_layer;
+    if (d.alpha_only) {     // the alpha row alone (row tile 0; row tile 1 is padding: 68 chunks = 0 mod 4), no view branch
+        c.l[c.n++] = {8, 0, 2, 1, 1};
+    } else {
+        if (d.split) {      // layer A = the alpha row (one row tile, one chunk), layer F = the 256 feature rows
+            c.l[c.n++] = {8, 0, 1, 1, 1};
+            c.l[c.n++] = std_layer;
+        } else {
+            c.l[c.n++] = {8, 0, 17, r_std, 257};                 // FA: feature | alpha
+        }
+        c.l[c.n++] = {8, 1, 8, r_v, 128};                        // V: cat([feature, views])
+        c.l[c.n++] = {4, 0, 1, 1, 3};                            // RGB
+    }
+    for (int li = 0; li < c.n; ++li) {
+        ChainLayer& L = c.l[li];
+        L.p3 = d.all_p3 || (d.mix && li >= 1 && li <= NERF_MIX_K);
+        if (d.mix && L.p3) L.rpc = li == 5 ? 1 : 2;
+        L.nj = (d.x1 || L.p3) ? 0 : L.ks / 2;
+    }
+    return c;
+}
+constexpr size_t chain_chunk_bytes(const ChainLayer& L) {      // 1 KiB pieces (layout: pack_chain below); a wave fetches ceil(pieces / 4) of them
+    const int pieces = L.p3 ? L.rpc * L.ks * 2 + L.rpc * L.nx * 2 : L.rpc * L.ks + L.rpc * L.nj + (L.rpc * L.nj + 1) / 2 + L.rpc * L.nx * 2;
+    return (size_t)((pieces + 3) / 4) * 4096;
+}
+// the table's hand-copied numbers against the layers: a stream size that is not the generator's, or a wrong layer count, does not compile
+constexpr bool chain_table_is_consistent() {
+    for (const NerfChainDesc& d : kNerfChain) {
+        const Chain c = chain_layers(d);
+        size_t bytes = 0;
+        for (int li = 0; li < c.n; ++li) bytes += (size_t)((c.l[li].rt + c.l[li].rpc - 1) / c.l[li].rpc) * chain_chunk_bytes(c.l[li]);
+        if (bytes != d.stream_bytes || c.n != d.n_layers) return false;
+    }
+    return true;
+}
+static_assert(chain_table_is_consistent(), "kNerfChain (nerf_common.h): a NERF_CHAIN*_STREAM_BYTES or n_layers is not what the format's layers add up to");
+constexpr NerfChainFmt chain_fmt_of_mode(int mode) {     // the full chain's stream of a precision mode
+    return mode == R2L_PREC_FP16X1 ? NERF_FMT_X1 : mode == R2L_PREC_FP16X3_ASM ? NERF_FMT_P3 : mode == R2L_PREC_FP16_MIX ? NERF_FMT_MIX : NERF_FMT_BF6;
+}
 
 struct ChainSrc {   // one layer's parameters: main(row, k), emb(row, embedding column), bias(row); rows < fan_out
     std::function<float(int, int)> main, emb;
@@ -124,23 +155,19 @@ struct ChainSrc {   // one layer's parameters: main(row, k), emb(row, embedding 
     bool is_pts;    // embedding k-steps: pts (nerf_pts_col) or view (nerf_view_col)
 };
 
-// fmt 1 (x1): the stream of R2L_PREC_FP16X1 -- the fp16 hi fragments and the embedding fragments only (NJ = 0), no scale bytes.
-// fmt 2 (p3): the stream of R2L_PREC_FP16X3_ASM -- per row tile its KS hi fragments, then its KS lo fragments, of W x 2^k with
+// NERF_FMT_X1: the stream of R2L_PREC_FP16X1 -- the fp16 hi fragments and the embedding fragments only (NJ = 0), no scale bytes.
+// NERF_FMT_P3: the stream of R2L_PREC_FP16X3_ASM -- per row tile its KS hi fragments, then its KS lo fragments, of W x 2^k with
 // max|w| 2^k in [2^12, 2^13) over the layer's main and embedding columns (lo = the fp16 rounding residual: a normal number thanks
 // to the factor); the bias x act_scale x 2^k; at the scale bytes' place 2^-k as a float for the epilogue
-// fmt 5 (p3s) / 6 (mixs): fmt 2 / 3 with the feature | alpha layer split (kChainP3S / kChainS: the alpha row first); the two halves' bf6 terms
+// NERF_FMT_P3S / _MIXS: _P3 / _MIX with the feature | alpha layer split (the alpha row first); the two halves' bf6 terms
 // keep the unsplit layer's weight exponent, so that the split chain computes bit for bit what the unsplit one does
-// fmt 4 (p3a): fmt 2 without the view branch (kChainP3A): nine layers, the last one the alpha row with its own 2^k
-// fmt 3 (mix): the stream of R2L_PREC_FP16_MIX -- fmt 0 with layers L1 .. L<NERF_MIX_K> packed as in fmt 2 (hi | lo fragments of
+// NERF_FMT_P3A: _P3 without the view branch: nine layers, the last one the alpha row with its own 2^k
+// NERF_FMT_MIX: the stream of R2L_PREC_FP16_MIX -- _BF6 with layers L1 .. L<NERF_MIX_K> packed as in _P3 (hi | lo fragments of
 // W x 2^k, 2^-k at the scale bytes' place) and 1.0f there for L0, whose epilogue hands L1 hi + lo sets with the three-pass form
-int pack_chain(const std::vector<std::vector<float>>& w, float Sa, std::vector<char>& img, int fmt = 0) {
-    const bool split = fmt == 5 || fmt == 6;
-    const bool mix = fmt == 3 || fmt == 6, alpha_only = fmt == 4;
-    const bool x1 = fmt == 1, all_p3 = fmt == 2 || alpha_only || fmt == 5;
-    const size_t stream_bytes = fmt == 5 ? NERF_CHAINP3S_STREAM_BYTES : fmt == 6 ? NERF_CHAINMS_STREAM_BYTES : alpha_only ? NERF_CHAINP3A_STREAM_BYTES
-                                : mix ? NERF_CHAINM_STREAM_BYTES : all_p3 ? NERF_CHAINP3_STREAM_BYTES
-                                : (x1 ? NERF_CHAINX_STREAM_BYTES : NERF_CHAIN_STREAM_BYTES);
-    const int n_layers = alpha_only ? 9 : split ? 12 : 11;
+int pack_chain(const std::vector<std::vector<float>>& w, float Sa, std::vector<char>& img, const NerfChainDesc& d) {
+    const bool split = d.split, mix = d.mix, alpha_only = d.alpha_only, x1 = d.x1;
+    const size_t stream_bytes = d.stream_bytes;
+    const Chain chain = chain_layers(d);
     img.assign(stream_bytes + NERF_CHAIN_AUX_BYTES, 0);
     auto mat = [&](int ti, int ncol, int col0) {
         const float* p = w[ti].data();
@@ -182,12 +209,11 @@ int pack_chain(const std::vector<std::vector<float>>& w, float Sa, std::vector<c
     }
     size_t chunk_off = 0;
     uint32_t* aux = reinterpret_cast<uint32_t*>(img.data() + stream_bytes);
-    for (int li = 0; li < n_layers; ++li) {
-        const ChainLayer& L = (fmt == 5 ? kChainP3S : fmt == 6 ? kChainS : alpha_only ? kChainP3A : all_p3 ? kChainP3 : (x1 ? kChainX : kChain))[li];
+    for (int li = 0; li < chain.n; ++li) {
+        const ChainLayer& L = chain.l[li];
         const ChainSrc& S = src[li];
-        const bool p3 = all_p3 || (mix && li >= 1 && li <= NERF_MIX_K);      // this layer's main k-steps run three fp16 passes
-        const int nj = (x1 || p3) ? 0 : L.ks / 2, K = L.ks * 32;
-        const int pieces = p3 ? L.rpc * L.ks * 2 + L.rpc * L.nx * 2 : L.rpc * L.ks + L.rpc * nj + (L.rpc * nj + 1) / 2 + L.rpc * L.nx * 2;
+        const bool p3 = L.p3;
+        const int nj = L.nj, K = L.ks * 32;
         float sw = 1.0f;
         if (p3) {
             float mx = 0.f;
@@ -199,7 +225,7 @@ int pack_chain(const std::vector<std::vector<float>>& w, float Sa, std::vector<c
             if (split && (li == 8 || li == 9)) mx = fa_max;        // the two halves of the feature | alpha layer keep the unsplit layer's 2^k
             sw = (mx > 0.f && isfinite(mx)) ? r2l_pow2_scale(&mx, 1) : 1.0f;
         }
-        const size_t chunk_bytes = (size_t)((pieces + 3) / 4) * 4096;
+        const size_t chunk_bytes = chain_chunk_bytes(L);
         uint32_t* al = aux + (size_t)li * NERF_CHAIN_AUX_LAYER / 4;
         for (int r = 0; r < L.fan_out; ++r) {
             const float v = (float)((double)S.bias(r) * Sa * (double)sw);
@@ -435,7 +461,7 @@ static int upload_img(PackedNet& net, int mode, const std::vector<char>& img) {
 static int build_net(nerf_ctx* c, PackedNet& net, int mode) {
     if (mode == R2L_PREC_FP16_FP8 || mode == R2L_PREC_FP16X1 || mode == R2L_PREC_FP16X3_ASM || mode == R2L_PREC_FP16_MIX) {  // the layer chain's own streams
         std::vector<char> img;
-        int rc = pack_chain(net.host_w, c->act_scale, img, mode == R2L_PREC_FP16X1 ? 1 : (mode == R2L_PREC_FP16X3_ASM ? 2 : (mode == R2L_PREC_FP16_MIX ? 3 : 0)));
+        int rc = pack_chain(net.host_w, c->act_scale, img, kNerfChain[chain_fmt_of_mode(mode)]);
         return rc ? rc : upload_img(net, mode, img);
     }
     const int np = np_of(mode);
@@ -553,14 +579,14 @@ int nerf_set_precision_pair(nerf_ctx* c, int coarse_mode, int fine_mode) {
     return ensure_alpha_img(c);
 }
 
-// nerf_set_skip_rgb0: the coarse network's three-pass stream without its view branch (pack_chain fmt 4), packed outside the render path
+// nerf_set_skip_rgb0: the coarse network's three-pass stream without its view branch (NERF_FMT_P3A), packed outside the render path
 static int ensure_alpha_img(nerf_ctx* c) {
     if (c->skip_rgb0) {      // ... and the fine network's stream with the second exit, for the mode it runs in
         PackedNet& f = c->net[1];
         const int fm = c->mode_net[1];
         if (f.loaded && (fm == R2L_PREC_FP16X3_ASM || fm == R2L_PREC_FP16_MIX) && f.exit_mode != fm) {
             std::vector<char> img;
-            int rc = pack_chain(f.host_w, c->act_scale, img, fm == R2L_PREC_FP16_MIX ? 6 : 5);
+            int rc = pack_chain(f.host_w, c->act_scale, img, kNerfChain[fm == R2L_PREC_FP16_MIX ? NERF_FMT_MIXS : NERF_FMT_P3S]);
             if (rc) return rc;
             if (f.d_img_exit) (void)hipFree(f.d_img_exit);
             f.d_img_exit = nullptr;
@@ -574,7 +600,7 @@ static int ensure_alpha_img(nerf_ctx* c) {
     PackedNet& n = c->net[0];
     if (!c->skip_rgb0 || !n.loaded || n.d_img_alpha || c->mode_net[0] != R2L_PREC_FP16X3_ASM) return R2L_OK;
     std::vector<char> img;
-    int rc = pack_chain(n.host_w, c->act_scale, img, 4);
+    int rc = pack_chain(n.host_w, c->act_scale, img, kNerfChain[NERF_FMT_P3A]);
     if (rc) return rc;
     hipError_t e = hipMalloc((void**)&n.d_img_alpha, img.size());
     if (e == hipSuccess) e = hipMemcpy(n.d_img_alpha, img.data(), img.size(), hipMemcpyHostToDevice);
@@ -870,7 +896,7 @@ int nerf_get_rays(int H, int W, double focal, const float* c2w_host, int row_beg
 
 // run_network (main.py:65-87) on explicit z values: raw [n, S, 4]
 long long nerf_debug_pack_chain_host(const float* const* tensors, int n_tensors, int fmt, char* out, long long cap, long long* offs) {
-    if (fmt < 0 || fmt > 6)
+    if (fmt < 0 || fmt >= NERF_CHAIN_FMTS)
         return r2l_set_error(R2L_EINVAL, "chain stream format %d (0 fp16 + bf6 terms, 1 fp16 only, 2 hi | lo, 3 mix, 4 hi | lo without the view branch, "
                              "5 / 6: 2 / 3 with the second exit behind the density)", fmt);
     if (!tensors || n_tensors != 24) return r2l_set_error(R2L_EINVAL, "expected 24 tensors");
@@ -880,9 +906,9 @@ long long nerf_debug_pack_chain_host(const float* const* tensors, int n_tensors,
         w.emplace_back(tensors[i], tensors[i] + kTensorNumel[i]);
     }
     std::vector<char> img;
-    int rc = pack_chain(w, 16.0f, img, fmt);
+    int rc = pack_chain(w, 16.0f, img, kNerfChain[fmt]);
     if (rc) return rc;
-    if (offs) offs[0] = fmt == 6 ? NERF_CHAINMS_STREAM_BYTES : fmt == 5 ? NERF_CHAINP3S_STREAM_BYTES : fmt == 4 ? NERF_CHAINP3A_STREAM_BYTES : fmt == 3 ? NERF_CHAINM_STREAM_BYTES : fmt == 2 ? NERF_CHAINP3_STREAM_BYTES : (fmt == 1 ? NERF_CHAINX_STREAM_BYTES : NERF_CHAIN_STREAM_BYTES);
+    if (offs) offs[0] = (long long)kNerfChain[fmt].stream_bytes;
     if (out && cap > 0) memcpy(out, img.data(), (size_t)(cap < (long long)img.size() ? cap : (long long)img.size()));
     return (long long)img.size();
 }

@@ -18,6 +18,8 @@
 //   V       feature(256) then view embedding(27+pad)  9   8  1096   relu
 //   RGB     128 -> 3                                  4   1  1168   (+12 unused fragments)
 #pragma once
+#include <stddef.h>
+
 #include "r2l_common.h"
 
 #define NERF_FRAGS_TOTAL 1184
@@ -46,12 +48,42 @@
 #define NERF_CHAINMS_STREAM_BYTES 2220032
 #define NERF_MIX_K 2
 #define NERF_CHAINM_STREAM_BYTES 2232320
+// The stream formats of the generated chain: the ONLY place the C++ side names them (the `fmt` column of VARIANTS in gen/nerf_gen.py,
+// which says what each one is; the values are ABI: nerf_debug_pack_chain_host(fmt)).  The three tilings of the fp16-only chain (two /
+// three / four column tiles per wave) share format 1.
+enum NerfChainFmt { NERF_FMT_BF6 = 0, NERF_FMT_X1, NERF_FMT_P3, NERF_FMT_MIX, NERF_FMT_P3A, NERF_FMT_P3S, NERF_FMT_MIXS, NERF_CHAIN_FMTS };
+// stream_bytes: the generator's STREAM_BYTES, copied by hand into the macros above (nerf_capi.hip derives it again from the flags and
+// refuses to compile a wrong one); x1: no bf6 terms; all_p3: every layer in three fp16 passes; mix: layers L1 .. L<NERF_MIX_K> only;
+// alpha_only: no view branch; split: the alpha row first, second exit behind it
+struct NerfChainDesc {
+    size_t stream_bytes;
+    bool x1, all_p3, mix, alpha_only, split;
+    int n_layers;
+};
+constexpr NerfChainDesc kNerfChain[NERF_CHAIN_FMTS] = {
+    {NERF_CHAIN_STREAM_BYTES, false, false, false, false, false, 11},     // NERF_FMT_BF6
+    {NERF_CHAINX_STREAM_BYTES, true, false, false, false, false, 11},     // NERF_FMT_X1
+    {NERF_CHAINP3_STREAM_BYTES, false, true, false, false, false, 11},    // NERF_FMT_P3
+    {NERF_CHAINM_STREAM_BYTES, false, false, true, false, false, 11},     // NERF_FMT_MIX
+    {NERF_CHAINP3A_STREAM_BYTES, false, true, false, true, false, 9},     // NERF_FMT_P3A
+    {NERF_CHAINP3S_STREAM_BYTES, false, true, false, false, true, 12},    // NERF_FMT_P3S
+    {NERF_CHAINMS_STREAM_BYTES, false, false, true, false, true, 12},     // NERF_FMT_MIXS
+};
+// the format whose row carries these flags (nerf_chain_kernel's template arguments); NERF_CHAIN_FMTS: no such chain exists
+constexpr NerfChainFmt nerf_chain_fmt(bool x1, bool p3, bool mix, bool alpha, bool skipv) {
+    for (int f = 0; f < NERF_CHAIN_FMTS; ++f) {
+        const NerfChainDesc& d = kNerfChain[f];
+        if (d.x1 == x1 && d.all_p3 == p3 && d.mix == mix && d.alpha_only == alpha && d.split == skipv) return (NerfChainFmt)f;
+    }
+    return NERF_CHAIN_FMTS;
+}
 #define NERF_CHAIN_AUX_BYTES 16384
 #define NERF_CHAIN_AUX_LAYER 1280   // per layer: 272 f32 bias | at byte 1152: 4 lane quarters x (swl, sw, 0, 0)
 #define NERF_CHAIN_AUX_SCALES 1152
 #define NERF_CHAIN_RING_BYTES (4 * 32768)
 #define NERF_CHAIN_LDS (NERF_CHAIN_RING_BYTES + NERF_CHAIN_AUX_BYTES)
 #define NERF_CHAIN_LDS_SKIP (NERF_CHAIN_LDS + 16)   // + the two LDS words the second exit's OR alternates between (at byte NERF_CHAIN_LDS)
+constexpr int nerf_chain_lds_bytes(NerfChainFmt f) { return kNerfChain[f].split ? NERF_CHAIN_LDS_SKIP : NERF_CHAIN_LDS; }
 #define NERF_N_SCALES 12  // L0..L7, FA, V, RGB (+1 spare)
 #define NERF_PTS_PER_WAVE 32
 #define NERF_TILE_PTS 128

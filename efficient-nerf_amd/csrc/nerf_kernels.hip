@@ -296,6 +296,7 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(NerfMlpParams p) {
 }
 
 // ------------------------------------------------------------------------------------
+// The hand-scheduled layer chain; its variants are listed in VARIANTS (gen/nerf_gen.py) and kNerfChain (nerf_common.h).
 // FP16_FP8: the hand-scheduled layer chain.  HIP code computes the tile's embedding fragments and stores raw; all
 // eleven layers of the tile are ONE inline-asm block generated by gen/nerf_gen.py (nerf_mlp_asm.inc): fixed register
 // map, fp16 main pass + bf6 x bf6 correction terms, three fp16 passes on the embedding k-steps, 4 x 32 KiB LDS ring fed
@@ -322,93 +323,76 @@ __global__ __launch_bounds__(256, 1) void nerf_mlp_kernel(NerfMlpParams p) {
 // and raw = (0, 0, 0, sigma).  The four waves agree through one of two LDS words (alternating per tile) and a barrier.
 template <bool X1, int NC, bool P3 = false, bool MIX = false, bool ALPHA = false, bool SKIPV = false>
 __global__ __launch_bounds__(256, 1) void nerf_chain_kernel(NerfMlpParams p) {
-    static_assert(!ALPHA || P3, "the chain without its view branch exists for the three-pass format");
-    static_assert(!SKIPV || ((P3 || MIX) && !ALPHA && NC == 2), "the second exit exists for the three-pass and the mixed chain");
-    static_assert(NC == 2 || (X1 && (NC == 3 || NC == 4)), "three / four column tiles exist for the fp16-only chain");
-    static_assert(!P3 || (!X1 && NC == 2), "the three-pass chain is a two-column-tile build");
-    static_assert(!MIX || (!X1 && !P3 && NC == 2), "the mixed chain is a two-column-tile build of the bf6 chain");
+    constexpr NerfChainFmt F = nerf_chain_fmt(X1, P3, MIX, ALPHA, SKIPV);      // the stream this build reads (nerf_common.h)
+    static_assert(F != NERF_CHAIN_FMTS, "no chain with these flags: kNerfChain has a row per combination that exists");
+    static_assert(NC == 2 || (F == NERF_FMT_X1 && (NC == 3 || NC == 4)), "three / four column tiles exist for the fp16-only chain");
     extern __shared__ __attribute__((aligned(16))) char nerf_chain_lds[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     {   // resident table: per layer 272 f32 bias (act_scale domain) | E8M0 weight scales (nerf_common.h)
-        const uint4* src = reinterpret_cast<const uint4*>(p.wimg + (SKIPV ? (MIX ? NERF_CHAINMS_STREAM_BYTES : NERF_CHAINP3S_STREAM_BYTES) : ALPHA ? NERF_CHAINP3A_STREAM_BYTES : MIX ? NERF_CHAINM_STREAM_BYTES : P3 ? NERF_CHAINP3_STREAM_BYTES : (X1 ? NERF_CHAINX_STREAM_BYTES : NERF_CHAIN_STREAM_BYTES)));
+        const uint4* src = reinterpret_cast<const uint4*>(p.wimg + kNerfChain[F].stream_bytes);
         uint4* dst = reinterpret_cast<uint4*>(nerf_chain_lds + NERF_CHAIN_RING_BYTES);
         for (int i = threadIdx.x; i < NERF_CHAIN_AUX_BYTES / 16; i += 256) dst[i] = src[i];
         if constexpr (SKIPV)
             if (threadIdx.x < 4) reinterpret_cast<unsigned*>(nerf_chain_lds + NERF_CHAIN_LDS)[threadIdx.x] = 0u;     // the second exit's two words
     }
     __syncthreads();
-    if constexpr (SKIPV && MIX) {
-        asm volatile(
-#include "nerf_mlpms_pro_asm.inc"
-            :
-            : [wimg] "s"(p.wimg), [wave] "s"(wave)
-            :
-#include "nerf_mlpms_pro_clobbers.inc"
-        );
-    } else if constexpr (SKIPV) {
-        asm volatile(
-#include "nerf_mlpp3s_pro_asm.inc"
-            :
-            : [wimg] "s"(p.wimg), [wave] "s"(wave)
-            :
-#include "nerf_mlpp3s_pro_clobbers.inc"
-        );
-    } else if constexpr (ALPHA) {
-        asm volatile(
-#include "nerf_mlpp3a_pro_asm.inc"
-            :
-            : [wimg] "s"(p.wimg), [wave] "s"(wave)
-            :
-#include "nerf_mlpp3a_pro_clobbers.inc"
-        );
-    } else if constexpr (MIX) {
-        asm volatile(
-#include "nerf_mlpm_pro_asm.inc"
-            :
-            : [wimg] "s"(p.wimg), [wave] "s"(wave)
-            :
-#include "nerf_mlpm_pro_clobbers.inc"
-        );
-    } else if constexpr (P3) {
-        asm volatile(
-#include "nerf_mlpp3_pro_asm.inc"
-            :
-            : [wimg] "s"(p.wimg), [wave] "s"(wave)
-            :
-#include "nerf_mlpp3_pro_clobbers.inc"
-        );
-    } else if constexpr (X1 && NC == 4) {
-        asm volatile(
-#include "nerf_mlpx4_pro_asm.inc"
-            :
-            : [wimg] "s"(p.wimg), [wave] "s"(wave)
-            :
-#include "nerf_mlpx4_pro_clobbers.inc"
-        );
-    } else if constexpr (X1 && NC == 3) {
-        asm volatile(
-#include "nerf_mlpx3_pro_asm.inc"
-            :
-            : [wimg] "s"(p.wimg), [wave] "s"(wave)
-            :
-#include "nerf_mlpx3_pro_clobbers.inc"
-        );
-    } else if constexpr (X1) {
-        asm volatile(
-#include "nerf_mlpx_pro_asm.inc"
-            :
-            : [wimg] "s"(p.wimg), [wave] "s"(wave)
-            :
-#include "nerf_mlpx_pro_clobbers.inc"
-        );
-    } else {
+    // the ladders below: one branch per variant in the order of the tables (the preprocessor cannot choose a file from a template argument)
+#define NERF_CHAIN_IN0 [wimg] "s"(p.wimg), [wave] "s"(wave)
+    if constexpr (F == NERF_FMT_BF6) {
         asm volatile(
 #include "nerf_mlp_pro_asm.inc"
-            :
-            : [wimg] "s"(p.wimg), [wave] "s"(wave)
-            :
+            : : NERF_CHAIN_IN0 :
 #include "nerf_mlp_pro_clobbers.inc"
+        );
+    } else if constexpr (F == NERF_FMT_X1 && NC == 2) {
+        asm volatile(
+#include "nerf_mlpx_pro_asm.inc"
+            : : NERF_CHAIN_IN0 :
+#include "nerf_mlpx_pro_clobbers.inc"
+        );
+    } else if constexpr (F == NERF_FMT_X1 && NC == 3) {
+        asm volatile(
+#include "nerf_mlpx3_pro_asm.inc"
+            : : NERF_CHAIN_IN0 :
+#include "nerf_mlpx3_pro_clobbers.inc"
+        );
+    } else if constexpr (F == NERF_FMT_X1 && NC == 4) {
+        asm volatile(
+#include "nerf_mlpx4_pro_asm.inc"
+            : : NERF_CHAIN_IN0 :
+#include "nerf_mlpx4_pro_clobbers.inc"
+        );
+    } else if constexpr (F == NERF_FMT_P3) {
+        asm volatile(
+#include "nerf_mlpp3_pro_asm.inc"
+            : : NERF_CHAIN_IN0 :
+#include "nerf_mlpp3_pro_clobbers.inc"
+        );
+    } else if constexpr (F == NERF_FMT_MIX) {
+        asm volatile(
+#include "nerf_mlpm_pro_asm.inc"
+            : : NERF_CHAIN_IN0 :
+#include "nerf_mlpm_pro_clobbers.inc"
+        );
+    } else if constexpr (F == NERF_FMT_P3A) {
+        asm volatile(
+#include "nerf_mlpp3a_pro_asm.inc"
+            : : NERF_CHAIN_IN0 :
+#include "nerf_mlpp3a_pro_clobbers.inc"
+        );
+    } else if constexpr (F == NERF_FMT_P3S) {
+        asm volatile(
+#include "nerf_mlpp3s_pro_asm.inc"
+            : : NERF_CHAIN_IN0 :
+#include "nerf_mlpp3s_pro_clobbers.inc"
+        );
+    } else {
+        static_assert(F == NERF_FMT_MIXS);
+        asm volatile(
+#include "nerf_mlpms_pro_asm.inc"
+            : : NERF_CHAIN_IN0 :
+#include "nerf_mlpms_pro_clobbers.inc"
         );
     }
     const float inv = 1.0f / p.act_scale;
@@ -434,91 +418,83 @@ __global__ __launch_bounds__(256, 1) void nerf_chain_kernel(NerfMlpParams p) {
             : [o0] "=&v"(o[0]), [o1] "=&v"(o[1]), [o2] "=&v"(o[2]), [o3] "=&v"(o[3]), [o4] "=&v"(o[4]), [o5] "=&v"(o[5]),         \
               [o6] "=&v"(o[6]), [o7] "=&v"(o[7])
 #define NERF_CHAIN_IN2                                                                                                            \
-            : [wimg] "s"(p.wimg), [wave] "s"(wave), [eh00] "a"(Eh[0][0]), [eh01] "a"(Eh[0][1]), [eh10] "a"(Eh[1][0]),             \
+            : NERF_CHAIN_IN0, [eh00] "a"(Eh[0][0]), [eh01] "a"(Eh[0][1]), [eh10] "a"(Eh[1][0]),                                   \
               [eh11] "a"(Eh[1][1]), [el00] "a"(El[0][0]), [el01] "a"(El[0][1]), [el10] "a"(El[1][0]), [el11] "a"(El[1][1]),       \
               [vh0] "a"(Vh[0][0]), [vh1] "a"(Vh[0][1]), [vl0] "a"(Vl[0][0]), [vl1] "a"(Vl[0][1])
         // the second exit's LDS word of this tile (its OR lives there; the other word is cleared for the next tile)
         const int fl = NERF_CHAIN_LDS + 4 * fl_parity;
         fl_parity ^= 1;
-        if constexpr (SKIPV && MIX) {
+        if constexpr (F == NERF_FMT_BF6) {
             asm volatile(
-#include "nerf_mlpms_asm.inc"
+#include "nerf_mlp_asm.inc"
                 NERF_CHAIN_OUT2
-                NERF_CHAIN_IN2, [fl] "s"(fl)
-                :
-#include "nerf_mlpms_clobbers.inc"
+                NERF_CHAIN_IN2 :
+#include "nerf_mlp_clobbers.inc"
             );
-        } else if constexpr (SKIPV) {
+        } else if constexpr (F == NERF_FMT_X1 && NC == 2) {
             asm volatile(
-#include "nerf_mlpp3s_asm.inc"
+#include "nerf_mlpx_asm.inc"
                 NERF_CHAIN_OUT2
-                NERF_CHAIN_IN2, [fl] "s"(fl)
-                :
-#include "nerf_mlpp3s_clobbers.inc"
+                NERF_CHAIN_IN2 :
+#include "nerf_mlpx_clobbers.inc"
             );
-        } else if constexpr (ALPHA) {
+        } else if constexpr (F == NERF_FMT_X1 && NC == 3) {
             asm volatile(
-#include "nerf_mlpp3a_asm.inc"
-                NERF_CHAIN_OUT2
-                NERF_CHAIN_IN2
-                :
-#include "nerf_mlpp3a_clobbers.inc"
+#include "nerf_mlpx3_asm.inc"
+                NERF_CHAIN_OUT2, [o8] "=&v"(o[8]), [o9] "=&v"(o[9]), [o10] "=&v"(o[10]), [o11] "=&v"(o[11])
+                NERF_CHAIN_IN2, [eh02] "a"(Eh[0][2]), [eh12] "a"(Eh[1][2]), [el02] "a"(El[0][2]), [el12] "a"(El[1][2]),
+                  [vh2] "a"(Vh[0][2]), [vl2] "a"(Vl[0][2]) :
+#include "nerf_mlpx3_clobbers.inc"
             );
-        } else if constexpr (MIX) {
-            asm volatile(
-#include "nerf_mlpm_asm.inc"
-                NERF_CHAIN_OUT2
-                NERF_CHAIN_IN2
-                :
-#include "nerf_mlpm_clobbers.inc"
-            );
-        } else if constexpr (P3) {
-            asm volatile(
-#include "nerf_mlpp3_asm.inc"
-                NERF_CHAIN_OUT2
-                NERF_CHAIN_IN2
-                :
-#include "nerf_mlpp3_clobbers.inc"
-            );
-        } else if constexpr (X1 && NC == 4) {
+        } else if constexpr (F == NERF_FMT_X1 && NC == 4) {
             asm volatile(
 #include "nerf_mlpx4_asm.inc"
                 NERF_CHAIN_OUT2, [o8] "=&v"(o[8]), [o9] "=&v"(o[9]), [o10] "=&v"(o[10]), [o11] "=&v"(o[11]), [o12] "=&v"(o[12]),
                   [o13] "=&v"(o[13]), [o14] "=&v"(o[14]), [o15] "=&v"(o[15])
                 NERF_CHAIN_IN2, [eh02] "a"(Eh[0][2]), [eh12] "a"(Eh[1][2]), [el02] "a"(El[0][2]), [el12] "a"(El[1][2]),
                   [vh2] "a"(Vh[0][2]), [vl2] "a"(Vl[0][2]), [eh03] "a"(Eh[0][3]), [eh13] "a"(Eh[1][3]), [el03] "a"(El[0][3]),
-                  [el13] "a"(El[1][3]), [vh3] "a"(Vh[0][3]), [vl3] "a"(Vl[0][3])
-                :
+                  [el13] "a"(El[1][3]), [vh3] "a"(Vh[0][3]), [vl3] "a"(Vl[0][3]) :
 #include "nerf_mlpx4_clobbers.inc"
             );
-        } else if constexpr (X1 && NC == 3) {
+        } else if constexpr (F == NERF_FMT_P3) {
             asm volatile(
-#include "nerf_mlpx3_asm.inc"
-                NERF_CHAIN_OUT2, [o8] "=&v"(o[8]), [o9] "=&v"(o[9]), [o10] "=&v"(o[10]), [o11] "=&v"(o[11])
-                NERF_CHAIN_IN2, [eh02] "a"(Eh[0][2]), [eh12] "a"(Eh[1][2]), [el02] "a"(El[0][2]), [el12] "a"(El[1][2]),
-                  [vh2] "a"(Vh[0][2]), [vl2] "a"(Vl[0][2])
-                :
-#include "nerf_mlpx3_clobbers.inc"
-            );
-        } else if constexpr (X1) {
-            asm volatile(
-#include "nerf_mlpx_asm.inc"
+#include "nerf_mlpp3_asm.inc"
                 NERF_CHAIN_OUT2
-                NERF_CHAIN_IN2
-                :
-#include "nerf_mlpx_clobbers.inc"
+                NERF_CHAIN_IN2 :
+#include "nerf_mlpp3_clobbers.inc"
+            );
+        } else if constexpr (F == NERF_FMT_MIX) {
+            asm volatile(
+#include "nerf_mlpm_asm.inc"
+                NERF_CHAIN_OUT2
+                NERF_CHAIN_IN2 :
+#include "nerf_mlpm_clobbers.inc"
+            );
+        } else if constexpr (F == NERF_FMT_P3A) {
+            asm volatile(
+#include "nerf_mlpp3a_asm.inc"
+                NERF_CHAIN_OUT2
+                NERF_CHAIN_IN2 :
+#include "nerf_mlpp3a_clobbers.inc"
+            );
+        } else if constexpr (F == NERF_FMT_P3S) {
+            asm volatile(
+#include "nerf_mlpp3s_asm.inc"
+                NERF_CHAIN_OUT2
+                NERF_CHAIN_IN2, [fl] "s"(fl) :
+#include "nerf_mlpp3s_clobbers.inc"
             );
         } else {
             asm volatile(
-#include "nerf_mlp_asm.inc"
+#include "nerf_mlpms_asm.inc"
                 NERF_CHAIN_OUT2
-                NERF_CHAIN_IN2
-                :
-#include "nerf_mlp_clobbers.inc"
+                NERF_CHAIN_IN2, [fl] "s"(fl) :
+#include "nerf_mlpms_clobbers.inc"
             );
         }
 #undef NERF_CHAIN_OUT2
 #undef NERF_CHAIN_IN2
+#undef NERF_CHAIN_IN0
         if (lane < 16) {
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
@@ -541,7 +517,7 @@ __global__ __launch_bounds__(256, 1) void nerf_chain_emb_kernel(NerfMlpParams p)
     extern __shared__ __attribute__((aligned(16))) char nerf_chain_lds[];
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     {   // resident table: per layer 272 f32 bias (act_scale domain) (nerf_common.h)
-        const uint4* src = reinterpret_cast<const uint4*>(p.wimg + NERF_CHAINX_STREAM_BYTES);
+        const uint4* src = reinterpret_cast<const uint4*>(p.wimg + kNerfChain[NERF_FMT_X1].stream_bytes);
         uint4* dst = reinterpret_cast<uint4*>(nerf_chain_lds + NERF_CHAIN_RING_BYTES);
         for (int i = threadIdx.x; i < NERF_CHAIN_AUX_BYTES / 16; i += 256) dst[i] = src[i];
     }
@@ -1064,42 +1040,43 @@ __global__ __launch_bounds__(256) void nerf_coarse_scan_kernel(const float* __re
 // ====================================================================================
 // launchers
 // ====================================================================================
-template <typename K>
-static hipError_t launch_big_lds(K kernel, std::atomic<bool>* attr_set, int lds, const NerfMlpParams& p, int grid,
-                                 hipStream_t stream) {
-    // the > 64 KiB dynamic-LDS opt-in is per device: a process may drive several GPUs
+template <auto Kernel>
+static hipError_t launch_big_lds(int lds, const NerfMlpParams& p, int grid, hipStream_t stream) {
+    // the > 64 KiB dynamic-LDS opt-in is per kernel and per device: a process may drive several GPUs
+    static std::atomic<bool> done[64];  // zero-initialised; the opt-in call itself is idempotent
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (dev < 0 || dev >= 64 || !done[dev]) {
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
         if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
+        if (dev >= 0 && dev < 64) done[dev] = true;
     }
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, stream, p);
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(256), lds, stream, p);
     return hipGetLastError();
+}
+
+template <bool X1, int NC, bool P3 = false, bool MIX = false, bool ALPHA = false, bool SKIPV = false>
+static hipError_t launch_chain(const NerfMlpParams& p, int grid, hipStream_t stream) {
+    return launch_big_lds<&nerf_chain_kernel<X1, NC, P3, MIX, ALPHA, SKIPV>>(nerf_chain_lds_bytes(nerf_chain_fmt(X1, P3, MIX, ALPHA, SKIPV)), p, grid, stream);
 }
 
 hipError_t nerf_launch_mlp(const NerfMlpParams& p, int mode, int grid, hipStream_t stream, int x1_col_tiles, bool stream_embed, bool alpha_only,
                            bool second_exit) {
-    static std::atomic<bool> attr_set[11][64];  // zero-initialised; the opt-in call itself is idempotent
-    if (second_exit && mode == R2L_PREC_FP16X3_ASM)
-        return launch_big_lds(&nerf_chain_kernel<false, 2, true, false, false, true>, attr_set[9], NERF_CHAIN_LDS_SKIP, p, grid, stream);
-    if (second_exit && mode == R2L_PREC_FP16_MIX)
-        return launch_big_lds(&nerf_chain_kernel<false, 2, false, true, false, true>, attr_set[10], NERF_CHAIN_LDS_SKIP, p, grid, stream);
-    if (alpha_only && mode == R2L_PREC_FP16X3_ASM)
-        return launch_big_lds(&nerf_chain_kernel<false, 2, true, false, true>, attr_set[8], NERF_CHAIN_LDS, p, grid, stream);
-    if (mode == R2L_PREC_FP16_MIX) return launch_big_lds(&nerf_chain_kernel<false, 2, false, true>, attr_set[7], NERF_CHAIN_LDS, p, grid, stream);
-    if (mode == R2L_PREC_FP16X3_ASM) return launch_big_lds(&nerf_chain_kernel<false, 2, true>, attr_set[6], NERF_CHAIN_LDS, p, grid, stream);
+    if (second_exit && mode == R2L_PREC_FP16X3_ASM) return launch_chain<false, 2, true, false, false, true>(p, grid, stream);
+    if (second_exit && mode == R2L_PREC_FP16_MIX) return launch_chain<false, 2, false, true, false, true>(p, grid, stream);
+    if (alpha_only && mode == R2L_PREC_FP16X3_ASM) return launch_chain<false, 2, true, false, true>(p, grid, stream);
+    if (mode == R2L_PREC_FP16_MIX) return launch_chain<false, 2, false, true>(p, grid, stream);
+    if (mode == R2L_PREC_FP16X3_ASM) return launch_chain<false, 2, true>(p, grid, stream);
     if (mode == R2L_PREC_FP16X1 && x1_col_tiles == 4 && stream_embed)
-        return launch_big_lds(&nerf_chain_emb_kernel, attr_set[5], NERF_CHAIN_LDS, p, grid, stream);
-    if (mode == R2L_PREC_FP16_FP8) return launch_big_lds(&nerf_chain_kernel<false, 2>, attr_set[0], NERF_CHAIN_LDS, p, grid, stream);
-    if (mode == R2L_PREC_FP16X3) return launch_big_lds(&nerf_mlp_kernel<2>, attr_set[1], KCfg<2>::LDS, p, grid, stream);
+        return launch_big_lds<&nerf_chain_emb_kernel>(nerf_chain_lds_bytes(NERF_FMT_X1), p, grid, stream);
+    if (mode == R2L_PREC_FP16_FP8) return launch_chain<false, 2>(p, grid, stream);
+    if (mode == R2L_PREC_FP16X3) return launch_big_lds<&nerf_mlp_kernel<2>>(KCfg<2>::LDS, p, grid, stream);
     // FP16X1: the generated chain without correction terms (round 4; the compiler-scheduled nerf_mlp_kernel<1> it replaces: 49.5 ms per
     // frame), with three column tiles per wave (192-point workgroup tiles: p.n_tiles counts those) or two
-    if (x1_col_tiles == 4) return launch_big_lds(&nerf_chain_kernel<true, 4>, attr_set[4], NERF_CHAIN_LDS, p, grid, stream);
-    if (x1_col_tiles == 3) return launch_big_lds(&nerf_chain_kernel<true, 3>, attr_set[3], NERF_CHAIN_LDS, p, grid, stream);
-    return launch_big_lds(&nerf_chain_kernel<true, 2>, attr_set[2], NERF_CHAIN_LDS, p, grid, stream);
+    if (x1_col_tiles == 4) return launch_chain<true, 4>(p, grid, stream);
+    if (x1_col_tiles == 3) return launch_chain<true, 3>(p, grid, stream);
+    return launch_chain<true, 2>(p, grid, stream);
 }
 
 hipError_t nerf_launch_ndc_rays(const float* rays_o, const float* rays_d, int n, int H, int W, double focal, float near_,

@@ -107,11 +107,7 @@ def test_cxx_packer_matches_python_restatement():
     assert np.array_equal(buf[aux_off:], aux)
 
 
-def test_committed_asm_is_the_generators_output(tmp_path):
-    G.emit(str(tmp_path), G.Opts())
-    for name in ('nerf_mlp_asm.inc', 'nerf_mlp_pro_asm.inc', 'nerf_mlp_clobbers.inc', 'nerf_mlp_pro_clobbers.inc'):
-        built = os.path.join(ROOT, 'efficient-nerf_amd', 'csrc', name)
-        assert open(os.path.join(str(tmp_path), name)).read() == open(built).read(), name
+# (the committed text against the generator's output: tests/test_nerf_genx_cpu.py, one test over every variant)
 
 
 @pytest.mark.parametrize('wave,n_tiles,gain', [(0, 1, 1.0), (3, 2, 1.0), (1, 1, 1.5)])

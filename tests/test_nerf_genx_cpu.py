@@ -38,9 +38,12 @@ def _load_x(fmt='f16'):
     return m
 
 
-GX = _load_x()
-G3 = _load_x('f16c3')      # three 16-point column tiles per wave: the same stream, 192-point tiles, activation set Q in AGPRs
-G4 = _load_x('f16c4')      # four: 256-point tiles (what R2L_PREC_FP16X1 launches)
+# one instance of the generator per row of its VARIANTS table (the bf6 one is test_nerf_gen_cpu's)
+INST = {name: (T.G if name == T.G.VARIANT else _load_x(name)) for name in T.G.VARIANTS}
+CSRC = os.path.join(ROOT, 'efficient-nerf_amd', 'csrc')
+GX = INST['f16']
+G3 = INST['f16c3']         # three 16-point column tiles per wave: the same stream, 192-point tiles, activation set Q in AGPRs
+G4 = INST['f16c4']         # four: 256-point tiles (what R2L_PREC_FP16X1 launches)
 
 
 def cxx_pack_x(tensors):
@@ -72,11 +75,30 @@ def test_cxx_packer_matches_python_restatement():
     assert cxx_pack_x(big)[0].size == buf.size
 
 
-def test_committed_asm_is_the_generators_output(tmp_path):
-    GX.emit(str(tmp_path), GX.Opts())
-    for name in ('nerf_mlpx_asm.inc', 'nerf_mlpx_pro_asm.inc', 'nerf_mlpx_clobbers.inc', 'nerf_mlpx_pro_clobbers.inc'):
-        built = os.path.join(ROOT, 'efficient-nerf_amd', 'csrc', name)
-        assert open(os.path.join(str(tmp_path), name)).read() == open(built).read(), name
+@pytest.mark.parametrize('name', list(T.G.VARIANTS))
+def test_committed_text_is_the_generators_output_and_the_cxx_table_agrees(name, tmp_path):
+    """per variant: every file it emits is the committed one byte for byte, and the row of its stream format in the C++ table
+    (csrc/nerf_common.h kNerfChain, through nerf_debug_pack_chain_host) carries the generator's stream size"""
+    G = INST[name]
+    (G.emit_kernel if G.EMB else G.emit)(str(tmp_path), G.Opts())
+    files = G.inc_files(name)
+    assert sorted(os.listdir(str(tmp_path))) == sorted(files) and len(files) == (2 if G.EMB else 4)
+    for f in files:
+        assert open(os.path.join(str(tmp_path), f), 'rb').read() == open(os.path.join(CSRC, f), 'rb').read(), f
+    keep, arr = _lib.host_ptrs([torch.from_numpy(x) for x in T.make_tensors(seed=1)])
+    offs = (C.c_longlong * 1)()
+    n = _lib.lib().nerf_debug_pack_chain_host(arr, len(keep), G.VARIANTS[name].fmt, None, 0, offs)
+    assert n == G.STREAM_BYTES + G.AUX_BYTES and offs[0] == G.STREAM_BYTES, _lib.lib().r2l_last_error()
+
+
+def test_every_committed_chain_text_belongs_to_a_variant_and_the_makefile_lists_the_variants():
+    V = T.G.VARIANTS
+    want = {f for name in V for f in T.G.inc_files(name)}
+    assert len(want) == 38 and {f for f in os.listdir(CSRC) if f.startswith('nerf_mlp') and f.endswith('.inc')} == want
+    assert sorted({v.fmt for v in V.values()}) == list(range(7))          # NerfChainFmt: every stream format has a variant
+    mk = dict(l.split(':=') for l in open(os.path.join(CSRC, 'Makefile')) if l.startswith(('NERF_VARIANTS :=', 'NERF_ONE_STATEMENT :=')))
+    assert mk['NERF_VARIANTS '].split() == ['%s:%s' % (v.suffix, name) for name, v in V.items()]
+    assert mk['NERF_ONE_STATEMENT '].split() == [v.suffix for v in V.values() if v.emb]
 
 
 @pytest.mark.parametrize('wave,n_tiles,gain', [(0, 1, 1.0), (3, 2, 1.0), (1, 1, 1.5)])
@@ -136,16 +158,12 @@ def make_frags_nc(G, e, v, act):
 
 
 @pytest.mark.parametrize('G', [G3, G4], ids=['three', 'four'])
-def test_more_column_tiles_layout_and_committed_text(G, tmp_path):
+def test_more_column_tiles_layout_and_committed_text(G):
     nc = G.NC
     assert G.X1 and G.N_ANCH == 1244 * nc and G.NCH == 44 and G.STREAM_BYTES == GX.STREAM_BYTES
     assert len(G.INPUT_NAMES) == 6 * nc and G.N_VGPR_CLOBBER + 4 * nc <= 256 and G.A_E + 24 * nc <= 256
     t = T.make_tensors(seed=9)
     assert np.array_equal(G.pack_teacher(t)[0], GX.pack_teacher(t)[0])          # the weight stream does not know about the tiling
-    G.emit(str(tmp_path), G.Opts())
-    for name in ('nerf_mlpx%d_asm.inc', 'nerf_mlpx%d_pro_asm.inc', 'nerf_mlpx%d_clobbers.inc', 'nerf_mlpx%d_pro_clobbers.inc'):
-        built = os.path.join(ROOT, 'efficient-nerf_amd', 'csrc', name % nc)
-        assert open(os.path.join(str(tmp_path), name % nc)).read() == open(built).read(), name % nc
 
 
 @pytest.mark.parametrize('G,wave,n_tiles,gain', [(G3, 0, 1, 1.0), (G3, 2, 2, 1.5), (G4, 1, 1, 1.0), (G4, 3, 2, 1.5)])
@@ -176,7 +194,7 @@ def test_emulated_wider_chain_vs_float64(G, wave, n_tiles, gain):
 
 
 # ---- f16p3: fp16x3's arithmetic on the generated chain (R2L_PREC_FP16X3_ASM of the teacher) --------------------------------------------
-GP = _load_x('f16p3')
+GP = INST['f16p3']
 
 
 def cxx_pack_fmt(tensors, fmt):
@@ -191,7 +209,7 @@ def cxx_pack_fmt(tensors, fmt):
     return buf, int(offs[0])
 
 
-def test_three_pass_chain_layout_packer_and_committed_text(tmp_path):
+def test_three_pass_chain_layout_packer_and_committed_text():
     assert GP.P3 and GP.NC == 2 and GP.NCH == 84 and GP.NCH % GP.NSLOT == 0 and GP.XPASS == 3 and GP.MPASS == 3
     assert GP.N_ANCH == (1100 + 72) * 3 * 2 == 7032       # 1,100 main and 72 embedding k-steps of the chain, three passes, two column tiles
     assert GP.STREAM_BYTES == 2433024                                         # NERF_CHAINP3_STREAM_BYTES (csrc/nerf_common.h)
@@ -201,10 +219,6 @@ def test_three_pass_chain_layout_packer_and_committed_text(tmp_path):
         img, aux = GP.pack_teacher(t)
         assert aux_off == img.size == GP.STREAM_BYTES and buf.size == img.size + aux.size
         assert np.array_equal(buf[:aux_off], img) and np.array_equal(buf[aux_off:], aux)
-    GP.emit(str(tmp_path), GP.Opts())
-    for name in ('nerf_mlpp3_asm.inc', 'nerf_mlpp3_pro_asm.inc', 'nerf_mlpp3_clobbers.inc', 'nerf_mlpp3_pro_clobbers.inc'):
-        built = os.path.join(ROOT, 'efficient-nerf_amd', 'csrc', name)
-        assert open(os.path.join(str(tmp_path), name)).read() == open(built).read(), name
 
 
 @pytest.mark.parametrize('wave,n_tiles,gain', [(0, 1, 1.0), (3, 2, 1.5), (2, 1, 2.5)])
@@ -235,10 +249,10 @@ def test_emulated_three_pass_chain_is_fp32_grade(wave, n_tiles, gain):
 
 
 # ---- mix: the bf6 chain with its first two trunk layers in three passes (R2L_PREC_FP16_MIX: the fine pass of trained teachers, round 6) ----
-GM = _load_x('mix')
+GM = INST['mix']
 
 
-def test_mixed_chain_layout_packer_and_committed_text(tmp_path):
+def test_mixed_chain_layout_packer_and_committed_text():
     assert GM.MIX and GM.MIXK == 2 and not GM.X1 and not GM.P3 and GM.NC == 2 and GM.NCH == 80 and GM.NCH % GM.NSLOT == 0
     assert [l.p3 for l in GM.CHAIN] == [False, True, True] + [False] * 8 and [l.lo_out for l in GM.CHAIN] == [True, True] + [False] * 9
     assert [l.uses_inv for l in GM.CHAIN] == [True, True, True] + [False] * 8 and [l.nj for l in GM.CHAIN] == [0, 0, 0, 4, 4, 4, 4, 4, 4, 4, 2]
@@ -255,11 +269,7 @@ def test_mixed_chain_layout_packer_and_committed_text(tmp_path):
         img, aux = GM.pack_teacher(t)
         assert aux_off == img.size == GM.STREAM_BYTES and buf.size == img.size + aux.size
         assert np.array_equal(buf[:aux_off], img) and np.array_equal(buf[aux_off:], aux)
-    GM.emit(str(tmp_path), GM.Opts())
-    for name in ('nerf_mlpm_asm.inc', 'nerf_mlpm_pro_asm.inc', 'nerf_mlpm_clobbers.inc', 'nerf_mlpm_pro_clobbers.inc'):
-        built = os.path.join(ROOT, 'efficient-nerf_amd', 'csrc', name)
-        assert open(os.path.join(str(tmp_path), name)).read() == open(built).read(), name
-    assert '"a224"' in open(os.path.join(ROOT, 'efficient-nerf_amd', 'csrc', 'nerf_mlpm_clobbers.inc')).read()        # the block owns a224-a255 too
+    assert '"a224"' in open(os.path.join(CSRC, 'nerf_mlpm_clobbers.inc')).read()        # the block owns a224-a255 too
 
 
 def _run_tile(G, buf, aux_off, e, v, wave=0, n_tiles=1):
@@ -323,10 +333,10 @@ def test_emulated_mixed_chain_on_the_trained_like_fine_network():
 
 
 # ---- f16p3a: the three-pass chain without its view branch (the coarse pass of renders whose caller drops rgb0: nerf_set_skip_rgb0) ----
-GA = _load_x('f16p3a')
+GA = INST['f16p3a']
 
 
-def test_alpha_only_chain_layout_packer_and_committed_text(tmp_path):
+def test_alpha_only_chain_layout_packer_and_committed_text():
     assert GA.ALPHA and GA.P3 and GA.NC == 2 and len(GA.CHAIN) == 9 and GA.CHAIN[-1].epi == 'alpha' and GA.CHAIN[-1].rt == 2 and GA.CHAIN[-1].fan_out == 1
     assert GA.NCH == 68 and GA.NCH % GA.NSLOT == 0 and GA.STREAM_BYTES == 1998848        # NERF_CHAINP3A_STREAM_BYTES (csrc/nerf_common.h)
     # the view branch's MFMAs are gone: 15 of FA's 17 row tiles, V, RGB
@@ -337,10 +347,6 @@ def test_alpha_only_chain_layout_packer_and_committed_text(tmp_path):
         img, aux = GA.pack_teacher(t)
         assert aux_off == img.size == GA.STREAM_BYTES and buf.size == img.size + aux.size
         assert np.array_equal(buf[:aux_off], img) and np.array_equal(buf[aux_off:], aux)
-    GA.emit(str(tmp_path), GA.Opts())
-    for name in ('nerf_mlpp3a_asm.inc', 'nerf_mlpp3a_pro_asm.inc', 'nerf_mlpp3a_clobbers.inc', 'nerf_mlpp3a_pro_clobbers.inc'):
-        built = os.path.join(ROOT, 'efficient-nerf_amd', 'csrc', name)
-        assert open(os.path.join(str(tmp_path), name)).read() == open(built).read(), name
 
 
 @pytest.mark.parametrize('wave,n_tiles,gain', [(0, 1, 1.0), (3, 2, 1.5)])
@@ -362,12 +368,12 @@ def test_emulated_alpha_only_chain_gives_the_full_chains_density_bit_for_bit(wav
 
 
 # ---- f16p3s / mixs: the chains with a second exit behind the density (tiles without a positive density skip the view branch) ----
-GS3 = _load_x('f16p3s')
-GSM = _load_x('mixs')
+GS3 = INST['f16p3s']
+GSM = INST['mixs']
 
 
 @pytest.mark.parametrize('G,fmt,base,stream', [(GS3, 5, 'p3', 2416640), (GSM, 6, 'm', 2220032)])
-def test_second_exit_chains_layout_packer_and_committed_text(tmp_path, G, fmt, base, stream):
+def test_second_exit_chains_layout_packer_and_committed_text(G, fmt, base, stream):
     assert G.SKIPV and [l.name for l in G.CHAIN] == ['L0', 'L1', 'L2', 'L3', 'L4', 'L5', 'L6', 'L7', 'A', 'F', 'V', 'RGB']
     assert G.CHAIN[8].rt == 1 and G.CHAIN[8].fan_out == 1 and G.CHAIN[9].rt == 16 and G.NCH % G.NSLOT == 0 and G.STREAM_BYTES == stream
     B_ = {'p3': GP, 'm': GM}[base]
@@ -378,11 +384,7 @@ def test_second_exit_chains_layout_packer_and_committed_text(tmp_path, G, fmt, b
         img, aux = G.pack_teacher(t)
         assert aux_off == img.size == G.STREAM_BYTES and buf.size == img.size + aux.size
         assert np.array_equal(buf[:aux_off], img) and np.array_equal(buf[aux_off:], aux)
-    G.emit(str(tmp_path), G.Opts())
-    for kind in ('asm', 'pro_asm', 'clobbers', 'pro_clobbers'):
-        name = 'nerf_mlp%ss_%s.inc' % (base, kind)
-        assert open(os.path.join(str(tmp_path), name)).read() == open(os.path.join(ROOT, 'efficient-nerf_amd', 'csrc', name)).read(), name
-    text = open(os.path.join(ROOT, 'efficient-nerf_amd', 'csrc', 'nerf_mlp%ss_asm.inc' % base)).read()
+    text = open(os.path.join(CSRC, G.inc_files(G.VARIANT)[0])).read()
     assert text.count('s_cbranch_scc1 L_skip_%=') == 1 and text.count('L_skip_%=:') == 1 and text.count('L_done_%=:') == 1 and '%[fl]' in text
     # every wave passes the same barriers whichever exit the workgroup takes: the cut's own barrier in front of the branch, then either the
     # rest of the full path or the second exit's single one
