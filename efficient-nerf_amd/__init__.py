@@ -1,5 +1,5 @@
 """efficient-nerf_amd: MI355X (gfx950) native renderer for the R2L / NeRF-teacher
-ray-batched inference path of MingSun-Tse/Efficient-NeRF.
+ray-batched path of MingSun-Tse/Efficient-NeRF, and trainer of the R2L student (train.py).
 
 The package directory name carries a hyphen (it is the repo's required layout); import it
 through ``_pkg.load()`` at the repo root, which registers it as ``efficient_nerf_amd``.
@@ -13,3 +13,4 @@ or eager fallback: if the library is missing or no gfx950 device is visible, cal
 from ._lib import lib, R2LError, PREC_FP16X3, PREC_FP16X1, PREC_FP16_FP8, PREC_FP16_E4M3, PREC_FP16X3_ASM, PREC_FP16_SPLIT, PREC_FP16_SPLIT8, PRECISIONS  # noqa: F401
 from .r2l import PointSampler, PositionalEmbedder, R2LEngine, NeRF_v3_2, render_func, PREC_NAMES  # noqa: F401
 from .teacher import NeRFEngine, get_rays, ndc_rays, raw2outputs, sample_pdf, merge_sorted, render  # noqa: F401
+from .train import R2LTrainer, HardRayPool, learning_rate  # noqa: F401

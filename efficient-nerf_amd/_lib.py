@@ -112,6 +112,17 @@ SIGNATURES = {
                                      C.c_longlong, _vp]),
     'r2l_sample_points': (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp]),
     'nerf_embed': (C.c_int, [_vp, C.c_longlong, C.c_int, C.c_int, C.c_int, _vp, C.c_longlong, _vp]),
+    # training (csrc/r2l_train.hip)
+    'r2l_linear_forward_dev': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_longlong, C.c_int, _vp, C.c_longlong, _vp, C.c_longlong,
+                                         C.c_float, C.c_int, _vp, C.c_longlong, _vp]),
+    'r2l_train_act_backward': (C.c_int, [_vp, C.c_longlong, _vp, C.c_longlong, _vp, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_float,
+                                         _vp, C.c_longlong, _vp, C.c_longlong, C.c_int, _vp, C.c_longlong, C.c_int, _vp]),
+    'r2l_train_grad_input': (C.c_int, [_vp, C.c_longlong, C.c_int, _vp, C.c_int, C.c_int, _vp, C.c_longlong, C.c_int, _vp]),
+    'r2l_train_grad_weight_slabs': (C.c_int, [C.c_int]),
+    'r2l_train_grad_weight': (C.c_int, [_vp, C.c_longlong, _vp, C.c_longlong, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp, C.c_longlong, _vp]),
+    'r2l_train_mse_loss': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_longlong, _vp]),
+    'r2l_train_adam': (C.c_int, [_vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_longlong, _vp]),
+    'r2l_train_jitter_z': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp]),
 }
 
 _lib = None

@@ -220,6 +220,29 @@ int r2l_linear_forward(const r2l_linear* l, const float* x_dev, long long ldx, i
     return R2L_OK;
 }
 
+// the same kernel on weights the caller keeps on the device (training: they change every step)
+int r2l_linear_forward_dev(const float* w_dev, const float* b_dev, int out_dim, int in_dim, const float* x_dev, long long ldx, int n,
+                           float* y_dev, long long ldy, const float* res_dev, long long ldr, float res_scale, int act,
+                           const float* post_dev, long long ldp, void* stream) {
+    if (!w_dev || !b_dev || (n != 0 && (!x_dev || !y_dev)) || n < 0 || out_dim <= 0 || in_dim <= 0 || out_dim > (1 << 16) || in_dim > (1 << 16) ||
+        ldx < in_dim || ldy < out_dim || (res_dev && ldr < out_dim) || (post_dev && ldp < out_dim) || act < R2L_ACT_NONE ||
+        act > R2L_ACT_SIGMOID)
+        return r2l_set_error(R2L_EINVAL, "bad argument to r2l_linear_forward_dev (n=%d ldx=%lld ldy=%lld act=%d; layer %d -> %d)", n, ldx,
+                             ldy, act, in_dim, out_dim);
+    const float* x_end = x_dev + (size_t)(n > 0 ? n - 1 : 0) * ldx + in_dim;
+    const float* y_end = y_dev + (size_t)(n > 0 ? n - 1 : 0) * ldy + out_dim;
+    if (n > 0 && x_dev < y_end && y_dev < x_end) return r2l_set_error(R2L_EINVAL, "r2l_linear_forward_dev: x and y overlap");
+    int rc = r2l_require_gfx950(nullptr);
+    if (rc) return rc;
+    if (n == 0) return R2L_OK;
+    dim3 grid((unsigned)((n + GT_M - 1) / GT_M), (unsigned)((out_dim + GT_N - 1) / GT_N));
+    hipLaunchKernelGGL(r2l_linear_kernel, grid, dim3(256), 0, (hipStream_t)stream, x_dev, ldx, n, in_dim, w_dev, b_dev, out_dim, y_dev, ldy,
+                       res_dev, ldr, res_scale, act, post_dev, ldp);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "r2l_linear_forward_dev launch: %s", hipGetErrorString(e));
+    return R2L_OK;
+}
+
 int r2l_sample_points(const float* rays_o_dev, const float* rays_d_dev, int n, const float* z_dev, int n_sample, int z_per_ray,
                       float* pts_out_dev, void* stream) {
     if (!rays_o_dev || !rays_d_dev || !z_dev || !pts_out_dev || n < 0 || n_sample <= 0)

@@ -69,6 +69,13 @@ FLAGS = [
     ('--debug', dict(action=_BOOL)), ('--no_batching', dict(action=_BOOL)), ('--lrate_decay', dict(type=int, default=250)),
     ('--N_rand', dict(type=int, default=4096)), ('--precrop_iters', dict(type=int, default=0)),
     ('--precrop_frac', dict(type=float, default=.5)), ('--no_reload', dict(action=_BOOL)),
+    # training (train.py; names and defaults of option.py).  --N_rand (shards per step under --data_mode rays) and --lrate_decay
+    # above are read by the training loop only; rendering ignores them.  --num_workers is accepted: the shards are read in-process.
+    ('--N_iters', dict(type=int, default=200000)), ('--lrate', dict(type=float, default=5e-4)), ('--warmup_lr', dict(type=str, default='')),
+    ('--hard_ratio', dict(type=str, default='')), ('--hard_mul', dict(type=float, default=1)), ('--datadir_kd', dict(type=str, default='')),
+    ('--pseudo_ratio', dict(type=float, default=-1.)), ('--data_mode', dict(type=str, default='images', choices=['images', 'rays'])),
+    ('--i_print', dict(type=int, default=100)), ('--i_weights', dict(type=int, default=10000)), ('--resume', dict(action=_BOOL)),
+    ('--num_workers', dict(type=int, default=8)),
     # this front-end's own knobs
     # auto (default): fp16_fp8 (fp16 MFMA pass + bf6 correction terms, 1.7x the speed) when the checkpoint's own activation
     # ranges, measured on every ray of the first frame and watched on every frame after it, keep it inside the 1e-4 rgb
@@ -734,7 +741,16 @@ def main(argv=None):
     from . import dist as D
     args = parse_args(argv)
     if not args.render_only:
-        raise SystemExit('this front-end implements the --render_only path (training is out of scope)')
+        if args.model_name not in ('R2L', 'nerf_v3.2'):
+            raise SystemExit(f'--model_name {args.model_name} without --render_only: teacher training is not built (the student trains: '
+                             f'--model_name R2L --data_mode rays --datadir_kd DIR)')
+        if args.data_mode != 'rays' or not args.datadir_kd:
+            raise SystemExit('without --render_only main.py trains the student, which is built for ray shards: pass --data_mode rays '
+                             '--datadir_kd DIR (or --render_only --pretrained_ckpt X.tar to render)')
+        from . import train as T
+        torch.cuda.set_device(D.local_device(0))
+        T.train(args, log=lambda *a, **k: print(*a, **k, flush=True))
+        return 0
     if not args.pretrained_ckpt:
         raise SystemExit('--pretrained_ckpt is required with --render_only')
     rank, local_rank, world = D.init()

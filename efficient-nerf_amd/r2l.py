@@ -788,7 +788,8 @@ class LazyEmbedding:
 
 class PointSampler:
     """model/nerf_raybased.py:76-126.  Same constructor; sample_test(c2w) and
-    sample_train(rays_o, rays_d, perturb=0) return lazy handles (see module docstring)."""
+    sample_train(rays_o, rays_d, perturb=0) return lazy handles (see module docstring);
+    sample_train with perturb > 0 (training) returns the jittered points as a tensor."""
 
     def __init__(self, H, W, focal, n_sample, near, far):
         if int(n_sample) < 1:
@@ -808,9 +809,18 @@ class PointSampler:
     def sample_test(self, c2w):  # c2w: [3, 4]
         return LazyPoints(self, c2w=c2w)
 
-    def sample_train(self, rays_o, rays_d, perturb):
-        if perturb > 0.:
-            raise NotImplementedError('perturb>0 is a training-only path (out of scope)')
+    def sample_train(self, rays_o, rays_d, perturb, t_rand=None):
+        if perturb > 0.:      # :117-123: jittered depths; the points are a tensor (the fused kernels sample fixed depths)
+            from .train import jitter_z_vals
+            ro, rd = rays_o.contiguous(), rays_d.contiguous()
+            n = ro.shape[0]
+            t_vals = torch.linspace(0., 1., steps=self.n_sample)      # :88-90 on the host, as the reference does
+            z_vals = (self.near * (1 - t_vals) + self.far * t_vals).to(ro.device)
+            pts = torch.empty((n, 3 * self.n_sample), dtype=torch.float32, device=ro.device)
+            with torch.cuda.device(ro.device):
+                z = jitter_z_vals(z_vals, n, t_rand)
+                check(lib().r2l_sample_points(dptr(ro), dptr(rd), n, dptr(z), self.n_sample, 1, dptr(pts), current_stream()))
+            return pts
         return LazyPoints(self, rays=(rays_o, rays_d))
 
 

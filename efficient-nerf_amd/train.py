@@ -1,0 +1,551 @@
+"""Training of the R2L student (main.py:1136-1513 with --model_name R2L / nerf_v3.2 and --data_mode rays): forward pass, backward
+pass, rgb loss and Adam as launches of the library's fp32 kernels (csrc/r2l_train.hip, include/r2l_hip.h).
+
+R2LTrainer holds every parameter in one flat device buffer (and likewise the gradients and Adam's two moments) with per-tensor
+views, plus the saved output of every layer for the backward pass.  torch supplies the buffers, the stream, the random draws
+(t_rand, the batch order) and index selection (the hard-ray pool's sort); every number of a step is computed by the library, in
+exact fp32 on the fp32 MFMA, and a step is bit-identical from run to run (the weight gradients are reduced over the rays in slabs
+that are added in a fixed order, not with atomics).
+
+The network description is generic.v3_2_plan's: every shape the reference's constructor accepts.
+"""
+import ctypes as C
+import math
+import os
+import time
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from ._lib import R2LError, check, current_stream, dptr, lib
+from .generic import _act_code, _strip, _view, v3_2_plan
+
+ADAM_BETAS = (0.9, 0.999)
+ADAM_EPS = 1e-8
+
+
+def jitter_z_vals(z_vals_dev, n, t_rand=None):
+    """PointSampler.sample_train's perturb > 0 branch (model/nerf_raybased.py:117-123): z [n, n_sample] on the device.
+    t_rand [n, n_sample] in [0, 1): the caller's, or a torch.rand draw on the device."""
+    S = z_vals_dev.shape[0]
+    dev = z_vals_dev.device
+    if t_rand is None:
+        t_rand = torch.rand((n, S), dtype=torch.float32, device=dev)
+    t_rand = t_rand.to(dev, torch.float32).contiguous()
+    if tuple(t_rand.shape) != (n, S):
+        raise R2LError(f't_rand is {tuple(t_rand.shape)}, expected {(n, S)}')
+    z = torch.empty((n, S), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().r2l_train_jitter_z(dptr(z_vals_dev), dptr(t_rand), n, S, dptr(z), current_stream()))
+    return z
+
+
+def init_state_dict(plan, seed=None):
+    """nn.Linear's default initialisation for every layer of a v3_2_plan, in plan order (what the reference's constructor leaves
+    in a freshly built NeRF_v3_2)."""
+    g = torch.random.get_rng_state()
+    if seed is not None:
+        torch.manual_seed(seed)
+    sd = OrderedDict()
+    for p in plan:
+        lin = torch.nn.Linear(p['in_dim'], p['out_dim'])
+        sd[p['key'] + '.weight'], sd[p['key'] + '.bias'] = lin.weight.detach().clone(), lin.bias.detach().clone()
+    if seed is not None:
+        torch.random.set_rng_state(g)
+    return sd
+
+
+class R2LTrainer:
+    """NeRF_v3_2 + PointSampler + PositionalEmbedder + MSE loss + torch.optim.Adam(betas (0.9, 0.999)) on the device.
+
+    max_rays: the largest batch a step may carry (the buffers are allocated once, at load_state_dict)."""
+
+    def __init__(self, near=2., far=6., n_sample=16, L=10, netdepth=88, netwidth=256, layerwise_netwidths='', act='relu',
+                 use_residual=True, trial=None, max_rays=1 << 14, device=None, z_vals=None):
+        if not torch.cuda.is_available():
+            raise R2LError('no HIP device visible to torch: training has no CPU fallback')
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.n_sample, self.L = int(n_sample), int(L)
+        if not 1 <= self.L <= 16 or self.n_sample < 1:
+            raise R2LError(f'n_sample={n_sample} multires={L}')
+        self.input_dim = 3 * self.n_sample * (2 * self.L + 1)
+        self.use_residual = bool(use_residual)
+        self.plan = v3_2_plan(netdepth, netwidth, self.input_dim, 3, layerwise_netwidths, act, use_residual, trial)
+        if len(self.plan) == 2 and self.use_residual:
+            raise R2LError('an empty body with --use_residual (netdepth < 4) is not built')
+        self.max_rays = int(max_rays)
+        if self.max_rays < 1:
+            raise R2LError(f'max_rays={max_rays}')
+        if z_vals is None:       # model/nerf_raybased.py:88-90, on the host as the reference does
+            t_vals = torch.linspace(0., 1., steps=self.n_sample)
+            z_vals = float(near) * (1 - t_vals) + float(far) * t_vals
+        self.z_vals = torch.as_tensor(z_vals).detach().to('cpu', torch.float32).contiguous()
+        # the first layer of the block a block_out layer closes
+        self._block_start = {}
+        start = None
+        for i, p in enumerate(self.plan):
+            if p.get('block_in'):
+                start = i
+            if p.get('block_out'):
+                self._block_start[i] = start
+        # flat layout: weight then bias, layer by layer (model.parameters() order)
+        self._slices = OrderedDict()
+        off = 0
+        for p in self.plan:
+            for kind, shape in (('weight', (p['out_dim'], p['in_dim'])), ('bias', (p['out_dim'],))):
+                cnt = int(np.prod(shape))
+                self._slices[f"{p['key']}.{kind}"] = (off, cnt, shape)
+                off += cnt
+        self.n_param = off
+        self.t = 0                # Adam updates so far
+        self.lr = 0.
+        self._param = None
+
+    # ---- state -------------------------------------------------------------------------------------------------------------
+    @property
+    def flops_per_ray(self):
+        """of the forward pass; a training step is about three times that (g_x and g_W cost one forward each)"""
+        return 2 * sum(p['in_dim'] * p['out_dim'] for p in self.plan)
+
+    def state_names(self):
+        return list(self._slices)
+
+    def activation_bytes(self, n=None):
+        n = self.max_rays if n is None else n
+        return 4 * n * (sum(p['out_dim'] for p in self.plan) + self.input_dim + 4 * self.n_sample)
+
+    def _views(self, flat):
+        return OrderedDict((k, flat[o:o + c].view(shape)) for k, (o, c, shape) in self._slices.items())
+
+    def _allocate(self):
+        n, dev = self.max_rays, self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        wmax = max(max(p['out_dim'], p['in_dim']) for p in self.plan[1:])
+        slabs = lib().r2l_train_grad_weight_slabs(n)
+        ws_floats = max(1, slabs * max(p['out_dim'] * p['in_dim'] + p['out_dim'] for p in self.plan))
+        want = self.activation_bytes() + 4 * (4 * self.n_param + 4 * n * wmax + ws_floats + 8 * n)
+        try:
+            with torch.cuda.device(dev):
+                self._param, self._grad, self._m, self._v = (torch.zeros(self.n_param, **f32) for _ in range(4))
+                self._acts = [torch.empty((n, p['out_dim']), **f32) for p in self.plan]
+                self._emb = torch.empty((n, self.input_dim), **f32)
+                self._pts = torch.empty((n, 3 * self.n_sample), **f32)
+                self._gbuf = [torch.empty((n, wmax), **f32) for _ in range(4)]     # R, Y, Z, P of forward_backward
+                self._gtail = torch.empty((n, 3), **f32)
+                self._err = torch.empty((n,), **f32)
+                self._loss = torch.zeros((1,), **f32)
+                self._ws = torch.empty((ws_floats,), **f32)
+                self._loss_ws = torch.empty(((n + 255) // 256,), **f32)
+                self._z_dev = self.z_vals.to(dev)
+        except (torch.cuda.OutOfMemoryError, RuntimeError) as e:
+            self._param = None
+            raise R2LError(f'cannot allocate the training buffers for {n} rays per step: about {want / 2 ** 30:.1f} GiB (saved layer '
+                           f'outputs {self.activation_bytes() / 2 ** 30:.1f} GiB: {len(self.plan)} layers; slab workspace '
+                           f'{4 * ws_floats / 2 ** 30:.2f} GiB): {e}. Lower --N_rand or the hard-ray share.') from e
+        self.p, self.g = self._views(self._param), self._views(self._grad)
+        self.exp_avg, self.exp_avg_sq = self._views(self._m), self._views(self._v)
+
+    def load_state_dict(self, state_dict):
+        sd = _strip(state_dict)
+        missing = [k for k in self._slices if k not in sd]
+        if missing:
+            raise R2LError(f'state_dict lacks {len(missing)} tensors, e.g. {missing[:3]} (has e.g. {sorted(sd)[:4]})')
+        for k, (_, _, shape) in self._slices.items():
+            if tuple(sd[k].shape) != tuple(shape):
+                raise R2LError(f'{k} is {tuple(sd[k].shape)}, the flags describe {tuple(shape)}')
+        if self._param is None:
+            self._allocate()
+        for k, v in self.p.items():
+            v.copy_(torch.as_tensor(sd[k]).detach().to(torch.float32))
+        return self
+
+    def state_dict(self):
+        """The weights on the host, keyed as the reference's network_fn_state_dict."""
+        self._need_state()
+        return OrderedDict((k, v.detach().cpu().clone()) for k, v in self.p.items())
+
+    def grads(self):
+        self._need_state()
+        return OrderedDict((k, v.detach().clone()) for k, v in self.g.items())
+
+    def _need_state(self):
+        if self._param is None:
+            raise R2LError('the trainer has no weights yet: load_state_dict first')
+
+    def optimizer_state_dict(self):
+        """torch.optim.Adam.state_dict(): parameters indexed in model.parameters() order (weight then bias, layer by layer)."""
+        self._need_state()
+        idx = list(range(len(self._slices)))
+        state = {}
+        if self.t > 0:
+            for i, k in enumerate(self._slices):
+                state[i] = {'step': torch.tensor(float(self.t)), 'exp_avg': self.exp_avg[k].detach().cpu().clone(),
+                            'exp_avg_sq': self.exp_avg_sq[k].detach().cpu().clone()}
+        group = {'lr': float(self.lr), 'betas': ADAM_BETAS, 'eps': ADAM_EPS, 'weight_decay': 0, 'amsgrad': False, 'maximize': False,
+                 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None, 'decoupled_weight_decay': False,
+                 'params': idx}
+        return {'state': state, 'param_groups': [group]}
+
+    def load_optimizer_state_dict(self, osd):
+        self._need_state()
+        groups = osd.get('param_groups', [])
+        n_par = sum(len(g['params']) for g in groups)
+        if n_par != len(self._slices):
+            raise R2LError(f'the optimizer state describes {n_par} parameters, this network has {len(self._slices)}')
+        for g in groups:
+            if tuple(g.get('betas', ADAM_BETAS)) != ADAM_BETAS or g.get('eps', ADAM_EPS) != ADAM_EPS or g.get('weight_decay', 0) != 0 \
+                    or g.get('amsgrad', False):
+                raise R2LError(f"the Adam built here has betas {ADAM_BETAS}, eps {ADAM_EPS}, no weight decay, no amsgrad; the state has "
+                               f"betas {g.get('betas')} eps {g.get('eps')} weight_decay {g.get('weight_decay')} amsgrad {g.get('amsgrad')}")
+        order = [i for g in groups for i in g['params']]
+        state = osd.get('state', {})
+        self._m.zero_()
+        self._v.zero_()
+        steps = set()
+        for pos, k in zip(order, self._slices):
+            st = state.get(pos)
+            if st is None:
+                continue
+            for name, dst in (('exp_avg', self.exp_avg[k]), ('exp_avg_sq', self.exp_avg_sq[k])):
+                if tuple(st[name].shape) != tuple(dst.shape):
+                    raise R2LError(f'optimizer state {pos} ({k}) {name} is {tuple(st[name].shape)}, expected {tuple(dst.shape)}')
+                dst.copy_(st[name].detach().to(torch.float32))
+            steps.add(int(float(st['step'])))
+        if len(steps) > 1 or (steps and len(state) != len(self._slices)):
+            raise R2LError(f'the optimizer state carries step counts {sorted(steps)} over {len(state)} of {len(self._slices)} parameters: '
+                           f'one flat Adam launch needs one count for all of them')
+        self.t = steps.pop() if steps else 0
+        if groups:
+            self.lr = float(groups[0].get('lr', self.lr))
+        return self
+
+    # ---- one step ----------------------------------------------------------------------------------------------------------
+    def _forward_layer(self, i, x, y, res=None, post=None):
+        p = self.plan[i]
+        xp, ldx = _view(x, p['in_dim'])
+        yp, ldy = _view(y, p['out_dim'])
+        rp, ldr = _view(res)
+        pp, ldp = _view(post)
+        check(lib().r2l_linear_forward_dev(dptr(self.p[p['key'] + '.weight']), dptr(self.p[p['key'] + '.bias']), p['out_dim'], p['in_dim'],
+                                           xp, ldx, x.shape[0], yp, ldy, rp, ldr, float(p.get('res_scale', 1.0)), _act_code(p['act']),
+                                           pp, ldp, current_stream()))
+
+    def forward(self, emb, n):
+        """NeRF_v3_2.forward (model/nerf_raybased.py:539-544) keeping every layer's output; returns rgb [n, 3] (a view)."""
+        acts = [a[:n] for a in self._acts]
+        self._forward_layer(0, emb, acts[0])
+        cur = acts[0]
+        last_body = len(self.plan) - 2
+        for i in range(1, last_body + 1):
+            p = self.plan[i]
+            if p.get('block_in'):
+                cur = acts[i - 1]
+            self._forward_layer(i, acts[i - 1], acts[i], res=cur if p.get('block_out') else None,
+                                post=acts[0] if (i == last_body and self.use_residual) else None)
+        self._forward_layer(len(self.plan) - 1, acts[-2], acts[-1])
+        return acts[-1]
+
+    def _grad_weight(self, i, gz, x):
+        p = self.plan[i]
+        n = x.shape[0]
+        zp, ldz = _view(gz, p['out_dim'])
+        xp, ldx = _view(x, p['in_dim'])
+        check(lib().r2l_train_grad_weight(zp, ldz, xp, ldx, n, p['out_dim'], p['in_dim'], dptr(self.g[p['key'] + '.weight']),
+                                          dptr(self.g[p['key'] + '.bias']), dptr(self._ws), self._ws.numel(), current_stream()))
+
+    def _grad_input(self, i, gz, gx, accumulate):
+        p = self.plan[i]
+        zp, ldz = _view(gz, p['out_dim'])
+        xp, ldx = _view(gx, p['in_dim'])
+        check(lib().r2l_train_grad_input(zp, ldz, gz.shape[0], dptr(self.p[p['key'] + '.weight']), p['out_dim'], p['in_dim'], xp, ldx,
+                                         1 if accumulate else 0, current_stream()))
+
+    def _act_backward(self, i, g_y, y, post, scale, g_z, g_res, res_acc, g_post):
+        p = self.plan[i]
+        w = p['out_dim']
+        gp, ldg = _view(g_y, w)
+        yp, ldy = _view(y, w)
+        pp, ldp = _view(post)
+        zp, ldz = _view(g_z, w)
+        rp, ldr = _view(g_res)
+        qp, ldq = _view(g_post)
+        check(lib().r2l_train_act_backward(gp, ldg, yp, ldy, pp, ldp, y.shape[0], w, _act_code(p['act']), float(scale), zp, ldz, rp, ldr,
+                                           1 if res_acc else 0, qp, ldq, 0, current_stream()))
+
+    def embed(self, rays_o, rays_d, perturb=1., t_rand=None):
+        """positional_embedder(point_sampler.sample_train(rays_o, rays_d, perturb)) into the trainer's buffer: [n, input_dim]"""
+        self._need_state()
+        n = rays_o.shape[0]
+        if n > self.max_rays:
+            raise R2LError(f'{n} rays in a step, the buffers were allocated for max_rays = {self.max_rays}')
+        ro = rays_o.to(self.device, torch.float32).contiguous()
+        rd = rays_d.to(self.device, torch.float32).contiguous()
+        pts, emb = self._pts[:n], self._emb[:n]
+        with torch.cuda.device(self.device):
+            if perturb > 0.:
+                z = jitter_z_vals(self._z_dev, n, t_rand)
+                check(lib().r2l_sample_points(dptr(ro), dptr(rd), n, dptr(z), self.n_sample, 1, dptr(pts), current_stream()))
+            else:
+                check(lib().r2l_sample_points(dptr(ro), dptr(rd), n, dptr(self._z_dev), self.n_sample, 0, dptr(pts), current_stream()))
+            check(lib().r2l_embed(dptr(pts), n, 3 * self.n_sample, self.L, dptr(emb), current_stream()))
+        return emb
+
+    def forward_backward(self, rays_o, rays_d, target, perturb=1., t_rand=None):
+        """loss (a one-element device tensor) of the batch; the gradients are left in the flat buffer (grads())."""
+        emb = self.embed(rays_o, rays_d, perturb, t_rand)
+        return self.forward_backward_embedded(emb, target)
+
+    def forward_backward_embedded(self, emb, target):
+        self._need_state()
+        n = emb.shape[0]
+        if n > self.max_rays:
+            raise R2LError(f'{n} rays in a step, the buffers were allocated for max_rays = {self.max_rays}')
+        tgt = target.to(self.device, torch.float32).contiguous()
+        if tuple(tgt.shape) != (n, 3):
+            raise R2LError(f'target is {tuple(tgt.shape)}, expected {(n, 3)}')
+        plan, nl = self.plan, len(self.plan)
+        last_body = nl - 2
+        with torch.cuda.device(self.device):
+            rgb = self.forward(emb, n)
+            acts = [a[:n] for a in self._acts]
+            R, Y, Z, P = (b[:n] for b in self._gbuf)
+            # loss, and through the tail's sigmoid: the tail layer's g_z
+            gz = self._gtail[:n]
+            check(lib().r2l_train_mse_loss(dptr(rgb), dptr(tgt), n, 1, dptr(gz), dptr(self._err[:n]), dptr(self._loss), dptr(self._loss_ws),
+                                           self._loss_ws.numel(), current_stream()))
+            self._grad_weight(nl - 1, gz, acts[-2])
+            g_y = R[:, :plan[-1]['in_dim']]
+            self._grad_input(nl - 1, gz, g_y, False)
+            # body, last layer first.  `stream`: the buffer the gradient of the open block's input is collected in (g_res, then
+            # the g_x of the block's first layer on top); P: the same for the head's output under --use_residual (g_post)
+            stream = None
+            for i in range(last_body, 0, -1):
+                p = plan[i]
+                w_out, w_in = p['out_dim'], p['in_dim']
+                has_res, has_post = bool(p.get('block_out')), i == last_body and self.use_residual
+                g_res = res_acc = None
+                if has_res:
+                    if self.use_residual and self._block_start[i] == 1:
+                        g_res, res_acc = P[:, :w_out], True          # block 0's input is the head's output: joins g_post
+                    else:
+                        g_res, res_acc = g_y, False                  # in place: g_u over g_y
+                    stream = g_res
+                z = Z[:, :w_out]
+                self._act_backward(i, g_y, acts[i], acts[0] if has_post else None, p.get('res_scale', 1.0) if has_res else 1.0, z,
+                                   g_res, res_acc, P[:, :w_out] if has_post else None)
+                self._grad_weight(i, z, acts[i - 1])
+                if p.get('block_in'):
+                    dst, acc = stream, True
+                elif i == 1 and self.use_residual:
+                    dst, acc = P[:, :w_in], True
+                else:
+                    dst, acc = Y[:, :w_in], False
+                self._grad_input(i, z, dst, acc)
+                g_y = dst
+            # head: no g_x (the embedding has no parameters)
+            z = Z[:, :plan[0]['out_dim']]
+            self._act_backward(0, g_y, acts[0], None, 1.0, z, None, False, None)
+            self._grad_weight(0, z, emb)
+        return self._loss
+
+    def adam(self, lr):
+        """One torch.optim.Adam update of every parameter from the gradients in the buffer."""
+        self._need_state()
+        self.t += 1
+        self.lr = float(lr)
+        with torch.cuda.device(self.device):
+            check(lib().r2l_train_adam(dptr(self._param), dptr(self._grad), dptr(self._m), dptr(self._v), self.n_param, float(lr), self.t,
+                                       current_stream()))
+
+    def step(self, rays_o, rays_d, target, lr, perturb=1., t_rand=None):
+        """forward_backward + Adam.  Returns (loss [1], err [n]): views of the trainer's buffers, valid until the next step;
+        err[r] = mean over the channels of (rgb - target)^2 from this step's forward pass (what the hard-ray pool sorts)."""
+        loss = self.forward_backward(rays_o, rays_d, target, perturb, t_rand)
+        self.adam(lr)
+        return loss, self._err[:rays_o.shape[0]]
+
+    @property
+    def rgb(self):
+        """the last forward pass's output buffer [max_rays, 3]"""
+        return self._acts[-1]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the loop of main.py:1136-1513
+# ---------------------------------------------------------------------------------------------------------------------------
+def learning_rate(step, lrate, lrate_decay, warmup_lr=''):
+    """main.py:1181-1195: linear warm-up from start_lr to lrate until end_iter, then 0.1 ** ((step - end_iter) / (lrate_decay * 1000))"""
+    decay_rate = 0.1
+    decay_steps = lrate_decay * 1000
+    if warmup_lr:
+        start_lr, end_iter = [float(x) for x in warmup_lr.split(',')]
+        if step < end_iter:
+            return (lrate - start_lr) / end_iter * step + start_lr
+        return lrate * (decay_rate ** ((step - end_iter) / decay_steps))
+    return lrate * (decay_rate ** (step / decay_steps))
+
+
+def parse_hard_ratio(text):
+    """option.py:379-383: '' -> None, 'r' -> float, 'in,out' -> [float, float]"""
+    if text in ('', None):
+        return None
+    if isinstance(text, (float, int, list)):
+        return text
+    return [float(x) for x in text.split(',')] if ',' in text else float(text)
+
+
+class HardRayPool:
+    """The hard-ray pool of main.py:1325-1347, 1410-1425: rows [rays_o | rays_d | target].  Until it holds batch_size * hard_mul
+    rows the n_hard_in worst rays of every batch are appended; from then on every batch is extended by n_hard_out rows drawn from
+    the pool, and n_hard_in of those drawn are replaced by the batch's worst rays."""
+
+    def __init__(self, hard_ratio, hard_mul=1.):
+        self.hard_ratio, self.hard_mul = parse_hard_ratio(hard_ratio), float(hard_mul)
+        self.rows = None
+        self.full = False
+        self._ix_out = None
+
+    def counts(self, batch_size):
+        if isinstance(self.hard_ratio, list):
+            n_in, n_out = int(self.hard_ratio[0] * batch_size), int(self.hard_ratio[1] * batch_size)
+        else:
+            n_in = n_out = int(self.hard_ratio * batch_size)
+        return min(n_in, n_out), n_out
+
+    def draw(self, batch_size):
+        """rows [n_hard_out, 9] to append to the batch, or None while the pool fills"""
+        if not self.full:
+            return None
+        _, n_out = self.counts(batch_size)
+        self._ix_out = np.random.permutation(self.rows.shape[0])[:n_out]
+        return self.rows[torch.as_tensor(self._ix_out, device=self.rows.device)]
+
+    def update(self, err, rays_o, rays_d, target, batch_size):
+        """err [>= batch_size]: the per-ray error of this step; only the batch's own rays (the first batch_size) are candidates"""
+        n_in, _ = self.counts(batch_size)
+        if n_in <= 0:
+            return
+        _, indices = torch.sort(err[:batch_size])
+        hard = indices[-n_in:]
+        rows = torch.cat([rays_o[hard], rays_d[hard], target[hard]], dim=-1)
+        if self.full:
+            self.rows[torch.as_tensor(self._ix_out[:n_in], device=self.rows.device)] = rows
+        else:
+            self.rows = rows if self.rows is None else torch.cat([self.rows, rows], dim=0)
+            if self.rows.shape[0] >= batch_size * self.hard_mul:
+                self.full = True
+
+
+def _infinite_order(n):
+    """main.py:759-767"""
+    order = np.random.permutation(n)
+    i = 0
+    while True:
+        yield order[i]
+        i += 1
+        if i == n:
+            order = np.random.permutation(n)
+            i = 0
+
+
+def save_train_checkpoint(path, trainer, global_step, best_psnr=0, best_psnr_step=0):
+    """The reference's schema (main.py:1516-1542) with the optimizer's state; without the pickled module, which the reference
+    only reads when it is there (main.py:484)."""
+    to_save = {'global_step': int(global_step), 'best_psnr': best_psnr, 'best_psnr_step': best_psnr_step,
+               'network_fn_state_dict': dict(trainer.state_dict()), 'optimizer_state_dict': trainer.optimizer_state_dict()}
+    tmp = path + '.tmp'
+    torch.save(to_save, tmp)
+    os.replace(tmp, path)
+    return path
+
+
+def trainer_from_args(args, max_rays):
+    if args.dataset_type == 'blender':
+        near, far = 2., 6.          # main.py:930-931
+    elif args.trial.near > 0 and args.trial.far > 0:
+        near, far = args.trial.near, args.trial.far
+    else:
+        raise R2LError(f'dataset_type={args.dataset_type}: training takes near / far from --trial.near and --trial.far')
+    if args.trial.near > 0:
+        near = args.trial.near
+    if args.trial.far > 0:
+        far = args.trial.far
+    if args.plucker or args.learn_depth or args.linear_tail:
+        raise R2LError('plucker / learn_depth / linear_tail variants are not built')
+    trial = None
+    if args.trial.ON:
+        trial = dict(body_arch=args.trial.body_arch, n_block=args.trial.n_block, n_learnable=int(args.trial.n_learnable),
+                     res_scale=float(args.trial.res_scale), inact=args.trial.inact, outact=args.trial.outact)
+    return R2LTrainer(near, far, n_sample=args.n_sample_per_ray, L=args.multires, netdepth=args.netdepth, netwidth=args.netwidth,
+                      layerwise_netwidths=args.layerwise_netwidths, act=args.act, use_residual=args.use_residual, trial=trial,
+                      max_rays=max_rays)
+
+
+def train(args, log=print):
+    """main.py without --render_only for --model_name R2L / nerf_v3.2, --data_mode rays."""
+    from .create_data import BlenderDataset_v2
+    from .frontend import load_checkpoint, mse2psnr
+    if args.data_mode != 'rays':
+        raise R2LError(f'--data_mode {args.data_mode}: training is built for --data_mode rays (the shards create_data.py writes)')
+    if not args.datadir_kd:
+        raise R2LError('training needs --datadir_kd (a directory of ray shards)')
+    datadir_kd = args.datadir_kd.split(':')[1] if ':' in args.datadir_kd else args.datadir_kd        # main.py:1052-1053
+    dataset = BlenderDataset_v2(datadir_kd, dim_dir=3, dim_rgb=3, pseudo_ratio=args.pseudo_ratio)
+    if len(dataset) == 0:
+        raise R2LError(f'no .npy shards under {datadir_kd}')
+    split = int(dataset[0][0].shape[0])
+    batch_size = args.N_rand * split
+    pool = HardRayPool(args.hard_ratio, args.hard_mul) if parse_hard_ratio(args.hard_ratio) else None
+    n_hard_out = pool.counts(batch_size)[1] if pool else 0
+    trainer = trainer_from_args(args, batch_size + n_hard_out)
+    dev = trainer.device
+    start = 0
+    if args.pretrained_ckpt:
+        ckpt = load_checkpoint(args.pretrained_ckpt)
+        trainer.load_state_dict(ckpt['network_fn_state_dict'])
+        log(f'Load pretrained ckpt successfully: "{args.pretrained_ckpt}".')
+        if args.resume:                                       # main.py:504-509
+            start = int(ckpt['global_step'])
+            trainer.load_optimizer_state_dict(ckpt['optimizer_state_dict'])
+            log('Resume optimizer successfully.')
+    else:
+        trainer.load_state_dict(init_state_dict(trainer.plan))
+    weights_dir = os.path.join(args.basedir, args.expname or 'train', 'weights')
+    os.makedirs(weights_dir, exist_ok=True)
+    log(f'Found {len(dataset)} shard(s) of {split} rays under "{datadir_kd}"; {args.N_rand} per step + {n_hard_out} hard rays; '
+        f'{trainer.n_param} parameters in {len(trainer.plan)} layers, {trainer.activation_bytes() / 2 ** 30:.2f} GiB of saved activations')
+    order = _infinite_order(len(dataset))
+    hist_psnr = 0.
+    t_data = t_batch = 0.
+    path = None
+    log('Begin training')
+    for i in range(start + 1, args.N_iters + 1):
+        t0 = time.time()
+        lr = learning_rate(i, args.lrate, args.lrate_decay, args.warmup_lr)
+        items = [dataset[int(next(order))] for _ in range(args.N_rand)]
+        rays_o, rays_d, target = (torch.cat([it[k] for it in items], 0).to(dev) for k in range(3))
+        if pool is not None:
+            picked = pool.draw(batch_size)
+            if picked is not None:
+                rays_o, rays_d, target = (torch.cat([a, picked[:, 3 * k:3 * k + 3]], 0) for k, a in enumerate((rays_o, rays_d, target)))
+        t_data = time.time() - t0
+        loss, err = trainer.step(rays_o, rays_d, target, lr, perturb=args.perturb)
+        if pool is not None:
+            pool.update(err, rays_o, rays_d, target, batch_size)
+        loss_v = float(loss.item())
+        t_batch = time.time() - t0
+        psnr = mse2psnr(loss_v)
+        if not math.isfinite(loss_v):
+            raise R2LError(f'the loss is {loss_v} at iteration {i} (LR {lr:.10f})')
+        hist_psnr = psnr if i == start + 1 else hist_psnr * 0.95 + psnr * 0.05
+        if i % args.i_print == 0:
+            log(f'[TRAIN] Iter {i} data_time {t_data:.4f} batch_time {t_batch:.4f} loss {loss_v:.6f} psnr {psnr:.4f} hist_psnr {hist_psnr:.4f} '
+                f'LR {lr:.10f}')
+        if i % args.i_weights == 0:
+            path = save_train_checkpoint(os.path.join(weights_dir, 'ckpt.tar'), trainer, i)
+            log(f'Iter {i} Save checkpoint: "{path}".')
+    if args.N_iters > start and args.N_iters % args.i_weights != 0:
+        path = save_train_checkpoint(os.path.join(weights_dir, 'ckpt.tar'), trainer, args.N_iters)
+        log(f'Iter {args.N_iters} Save checkpoint: "{path}".')
+    return path

@@ -458,6 +458,43 @@ int r2l_sample_points(const float* rays_o_dev, const float* rays_d_dev, int n, c
  * sin(2 x), cos(2 x), ..., cos(2^(multires-1) x)] of x = x_dev[r, :dim]; row strides ldi / ldo in floats */
 int nerf_embed(const float* x_dev, long long ldi, int n, int dim, int multires, float* out_dev, long long ldo, void* stream);
 
+/* ---- training of the R2L student (csrc/r2l_train.hip; host mirror: efficient-nerf_amd/train.py) ----
+ * Exact fp32 on the fp32 MFMA, one launch per layer and direction, every buffer the caller's.  Nothing here uses float atomics:
+ * the same inputs give the same bits.  With n = 0 the per-ray buffers may be NULL (an empty batch: g_W and g_b become zero). */
+/* r2l_linear_forward on weights that live in caller device buffers (w_dev [out_dim, in_dim], b_dev [out_dim]) */
+int r2l_linear_forward_dev(const float* w_dev, const float* b_dev, int out_dim, int in_dim, const float* x_dev, long long ldx, int n,
+                           float* y_dev, long long ldy, const float* res_dev, long long ldr, float res_scale, int act,
+                           const float* post_dev, long long ldp, void* stream);
+/* The element-wise part of a layer's backward pass.  The layer computed y = post + act(u), u = scale * lin + res.  Given g_y:
+ *   g_post = g_y (+ g_post when post_accumulate);  g_u = g_y * act'(y - post);  g_res = g_u (+ g_res when res_accumulate);
+ *   g_z = scale * g_u.
+ * post_dev / g_res_dev / g_post_dev may be NULL.  g_res_dev may be g_y_dev (in place), and g_post_dev may be g_res_dev (it then
+ * receives g_y + g_u).  act' from the saved output: relu a > 0, lrelu a > 0 ? 1 : 0.01, none 1, sigmoid a (1 - a). */
+int r2l_train_act_backward(const float* g_y_dev, long long ldg, const float* y_dev, long long ldy, const float* post_dev,
+                           long long ldp, int n, int width, int act, float scale, float* g_z_dev, long long ldz, float* g_res_dev,
+                           long long ldr, int res_accumulate, float* g_post_dev, long long ldq, int post_accumulate, void* stream);
+/* g_x [n, in_dim] = g_z [n, out_dim] W [out_dim, in_dim] (+ g_x when accumulate: gradients that meet on one stream add up) */
+int r2l_train_grad_input(const float* g_z_dev, long long ldz, int n, const float* w_dev, int out_dim, int in_dim, float* g_x_dev,
+                         long long ldgx, int accumulate, void* stream);
+/* g_W [out_dim, in_dim] = g_z^T x and g_b [out_dim] = the column sums of g_z (g_b_dev may be NULL), overwritten.  The rays are cut
+ * into r2l_train_grad_weight_slabs of n slabs -- a function of n alone -- whose partial results go to workspace_dev (slabs *
+ * (out_dim * in_dim + out_dim) floats) and are added in slab order by a second kernel. */
+int r2l_train_grad_weight_slabs(int n);
+int r2l_train_grad_weight(const float* g_z_dev, long long ldz, const float* x_dev, long long ldx, int n, int out_dim, int in_dim,
+                          float* g_w_dev, float* g_b_dev, float* workspace_dev, long long workspace_floats, void* stream);
+/* loss_dev[0] = mean over n x 3 of (rgb - target)^2; g_out_dev [n, 3] = 2 (rgb - target) / (3 n), times rgb (1 - rgb) when
+ * through_sigmoid (the tail layer's g_z directly); err_dev [n] (may be NULL) = the mean over the channels of (rgb - target)^2.
+ * workspace_dev: ceil(n / 256) floats. */
+int r2l_train_mse_loss(const float* rgb_dev, const float* target_dev, int n, int through_sigmoid, float* g_out_dev, float* err_dev,
+                       float* loss_dev, float* workspace_dev, long long workspace_floats, void* stream);
+/* torch.optim.Adam's update with betas (0.9, 0.999), eps 1e-8, no weight decay, no amsgrad over `count` parameters in flat
+ * buffers; step = the 1-based count of updates including this one */
+int r2l_train_adam(float* param_dev, const float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, long long count, double lr,
+                   long long step, void* stream);
+/* PointSampler.sample_train with perturb > 0 (model/nerf_raybased.py:117-123): z_out [n, n_sample] = lower + (upper - lower) *
+ * t_rand over the strata of z_vals_dev [n_sample]; feeds r2l_sample_points with z_per_ray = 1 */
+int r2l_train_jitter_z(const float* z_vals_dev, const float* t_rand_dev, int n, int n_sample, float* z_out_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

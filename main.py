@@ -1,7 +1,7 @@
 #!/usr/bin/env python
-"""Entry point with the reference's command line for the render-only path
-(`--render_only [--render_test]`, `--config configs/*.txt`, `--pretrained_ckpt X.tar`);
-see efficient-nerf_amd/frontend.py."""
+"""Entry point with the reference's command line: the render-only path
+(`--render_only [--render_test]`, `--config configs/*.txt`, `--pretrained_ckpt X.tar`) and, without `--render_only`,
+training of the R2L student (`--data_mode rays --datadir_kd DIR`); see efficient-nerf_amd/frontend.py and train.py."""
 import os
 import sys
 
