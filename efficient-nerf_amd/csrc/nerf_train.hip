@@ -1,0 +1,170 @@
+// Training of the NeRF teacher (main.py:624-756, 1353-1406) in exact fp32: the one stage of a teacher step the student's
+// training kernels (r2l_train.hip) do not cover, the backward pass of the volume-rendering scan raw2outputs (main.py:556-621).
+// The host mirror composes the step (efficient-nerf_amd/train_teacher.py).
+//
+// Forward (nerf_raw2outputs_kernel): c = sigmoid(raw_rgb), s = relu(raw_sigma + noise), alpha = 1 - exp(-s dist),
+// p = 1 - alpha + 1e-10, T_i = prod_{j<i} p_j, w = alpha T, rgb_map = sum_i w_i c_i (+ 1 - sum_i w_i on a white background).
+// The loss reaches rgb_map alone (z_samples is detached, main.py:728), so with g = g_rgb_map and
+//   q_i = g . c_i - (white_bkgd ? g_r + g_g + g_b : 0)                      (= dL/dw_i)
+//   g_c_i     = w_i g                                                       through c (1 - c)
+//   g_alpha_i = T_i (q_i - B_i),   B_i = alpha_{i+1} q_{i+1} + p_{i+1} B_{i+1},  B_{S-1} = 0
+//   g_s_i     = g_alpha_i * (dist_i exp(-s_i dist_i))                       through relu' (0 at 0, as torch)
+// B is the division-free form of cumprod's backward: autograd's reverse_cumsum(grad * out) / in divides by p = 1e-10 on a
+// saturated sample.
+//
+// Layout as the forward scan: a wave owns a ray, lane l of chunk k owns sample 64 k + l (a coalesced float4 of raw per lane), any
+// S >= 1.  Pass 1 walks the chunks front to back: T (cumprod accumulated in double and rounded per element, as the forward kernel
+// does) is parked in the density slot of the sample's own g_raw element.  Pass 2 walks them back to front: the forward quantities
+// are recomputed in registers, B is a suffix scan of the affine maps E -> alpha q + p E across the wave (in double) with the carry
+// E of the chunk behind, and every g_raw element is written once, whole.  No atomics, no reduction across rays: the same
+// inputs give the same bits.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/r2l_hip.h"
+#include "r2l_host_util.h"
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ double nt_shfl_up_f64(double v, int delta) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __shfl_up(lo, delta, 64);
+    hi = __shfl_up(hi, delta, 64);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double nt_shfl_down_f64(double v, int delta) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __shfl_down(lo, delta, 64);
+    hi = __shfl_down(hi, delta, 64);
+    return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ double nt_shfl_f64(double v, int src) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __shfl(lo, src, 64);
+    hi = __shfl(hi, src, 64);
+    return __hiloint2double(hi, lo);
+}
+
+// alpha and dist * exp(-s dist) of sample i (i < S) as the forward kernel computes alpha
+struct NtSample {
+    float alpha, dalpha;   // dalpha = d alpha / d raw_sigma (0 where the relu is closed)
+};
+__device__ __forceinline__ NtSample nt_sample(const float* __restrict__ zr, const float* __restrict__ noise_r, float raw_sigma, int i,
+                                              int S, float norm) {
+    float dist = (i < S - 1) ? (zr[i + 1] - zr[i]) : 1e10f;   // dists = cat(z[1:] - z[:-1], 1e10)
+    dist = dist * norm;
+    const float pre = noise_r ? raw_sigma + noise_r[i] : raw_sigma;
+    const float sig = fmaxf(pre, 0.0f);
+    const float e = expf(-sig * dist);
+    NtSample o;
+    o.alpha = 1.0f - e;
+    o.dalpha = pre > 0.0f ? dist * e : 0.0f;
+    return o;
+}
+
+__global__ __launch_bounds__(256) void nerf_raw2outputs_backward_kernel(const float* __restrict__ raw, const float* __restrict__ z,
+                                                                        const float* __restrict__ rays_d,
+                                                                        const float* __restrict__ noise, int n, int S, int white_bkgd,
+                                                                        const float* __restrict__ g_rgb_map, float* g_raw) {
+    const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (ray >= n) return;
+    const float* zr = z + (size_t)ray * S;
+    const float* nr = noise ? noise + (size_t)ray * S : nullptr;
+    const float* rr = raw + (size_t)ray * S * 4;
+    float* gr = g_raw + (size_t)ray * S * 4;
+    const float dx = rays_d[(size_t)ray * 3 + 0], dy = rays_d[(size_t)ray * 3 + 1], dz = rays_d[(size_t)ray * 3 + 2];
+    const float norm = sqrtf(__fadd_rn(__fadd_rn(dx * dx, dy * dy), dz * dz));
+    const float g0 = g_rgb_map[(size_t)ray * 3 + 0], g1 = g_rgb_map[(size_t)ray * 3 + 1], g2 = g_rgb_map[(size_t)ray * 3 + 2];
+    const float gsum = white_bkgd ? (g0 + g1) + g2 : 0.0f;
+    const int n_chunk = (S + 63) >> 6;
+
+    // pass 1: T_i into g_raw[i][3]
+    double carry = 1.0;
+    for (int k = 0; k < n_chunk; ++k) {
+        const int i = k * 64 + lane;
+        const bool ok = i < S;
+        double pterm = 1.0;
+        if (ok) {
+            const NtSample sm = nt_sample(zr, nr, rr[(size_t)i * 4 + 3], i, S, norm);
+            pterm = (double)((1.0f - sm.alpha) + 1e-10f);
+        }
+        double incl = pterm;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const double u = nt_shfl_up_f64(incl, d);
+            if (lane >= d) incl *= u;
+        }
+        double excl = nt_shfl_up_f64(incl, 1);
+        if (lane == 0) excl = 1.0;
+        if (ok) gr[(size_t)i * 4 + 3] = (float)(carry * excl);
+        carry *= nt_shfl_f64(incl, 63);
+    }
+
+    // pass 2: E_i = alpha_i q_i + p_i E_{i+1}, E_S = 0; B_i = E_{i+1}
+    double e_behind = 0.0;
+    for (int k = n_chunk - 1; k >= 0; --k) {
+        const int i = k * 64 + lane;
+        const bool ok = i < S;
+        f32x4 r4 = {0.f, 0.f, 0.f, 0.f};
+        NtSample sm = {0.f, 0.f};
+        float T = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, q = 0.f;
+        double a = 0.0, p = 1.0;               // the identity map on the lanes behind the ray's end
+        if (ok) {
+            r4 = *reinterpret_cast<const f32x4*>(rr + (size_t)i * 4);
+            sm = nt_sample(zr, nr, r4[3], i, S, norm);
+            T = gr[(size_t)i * 4 + 3];         // this lane's own store of pass 1
+            c0 = 1.0f / (1.0f + expf(-r4[0]));
+            c1 = 1.0f / (1.0f + expf(-r4[1]));
+            c2 = 1.0f / (1.0f + expf(-r4[2]));
+            q = ((g0 * c0 + g1 * c1) + g2 * c2) - gsum;
+            a = (double)sm.alpha * (double)q;
+            p = (double)((1.0f - sm.alpha) + 1e-10f);
+        }
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {     // (a, p) of lane l := the map of samples l .. min(l + 2d - 1, 63) of the chunk
+            const double a2 = nt_shfl_down_f64(a, d), p2 = nt_shfl_down_f64(p, d);
+            if (lane + d < 64) {
+                a = a + p * a2;
+                p = p * p2;
+            }
+        }
+        const double E = a + p * e_behind;
+        double B = nt_shfl_down_f64(E, 1);
+        if (lane == 63) B = e_behind;
+        e_behind = nt_shfl_f64(E, 0);
+        if (ok) {
+            const float w = sm.alpha * T;
+            const float g_alpha = T * (float)((double)q - B);
+            f32x4 o;
+            o[0] = (w * g0) * (c0 * (1.0f - c0));
+            o[1] = (w * g1) * (c1 * (1.0f - c1));
+            o[2] = (w * g2) * (c2 * (1.0f - c2));
+            o[3] = sm.dalpha == 0.0f ? 0.0f : g_alpha * sm.dalpha;
+            *reinterpret_cast<f32x4*>(gr + (size_t)i * 4) = o;
+        }
+    }
+}
+
+extern "C" {
+
+int nerf_train_raw2outputs_backward(const float* raw_dev, const float* z_dev, const float* rays_d_dev, const float* noise_dev, int n,
+                                    int S, int white_bkgd, const float* g_rgb_map_dev, float* g_raw_dev, void* stream) {
+    if ((n != 0 && (!raw_dev || !z_dev || !rays_d_dev || !g_rgb_map_dev || !g_raw_dev)) || n < 0 || S < 1 ||
+        (long long)n * S > (1LL << 40))
+        return r2l_set_error(R2L_EINVAL, "bad argument to nerf_train_raw2outputs_backward (n=%d S=%d)", n, S);
+    if (((uintptr_t)raw_dev | (uintptr_t)g_raw_dev) & 15)
+        return r2l_set_error(R2L_EINVAL, "nerf_train_raw2outputs_backward: raw and g_raw must be 16-byte aligned");
+    if (n > 0 && raw_dev == g_raw_dev) return r2l_set_error(R2L_EINVAL, "nerf_train_raw2outputs_backward: g_raw must not be raw");
+    int rc = r2l_require_gfx950(nullptr);
+    if (rc) return rc;
+    if (n == 0) return R2L_OK;
+    hipLaunchKernelGGL(nerf_raw2outputs_backward_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, raw_dev, z_dev,
+                       rays_d_dev, noise_dev, n, S, white_bkgd ? 1 : 0, g_rgb_map_dev, g_raw_dev);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "nerf_train_raw2outputs_backward launch: %s", hipGetErrorString(e));
+    return R2L_OK;
+}
+
+}  // extern "C"

@@ -76,6 +76,10 @@ FLAGS = [
     ('--pseudo_ratio', dict(type=float, default=-1.)), ('--data_mode', dict(type=str, default='images', choices=['images', 'rays'])),
     ('--i_print', dict(type=int, default=100)), ('--i_weights', dict(type=int, default=10000)), ('--resume', dict(action=_BOOL)),
     ('--num_workers', dict(type=int, default=8)),
+    # teacher training (train_teacher.py; names and defaults of option.py).  --no_batching, --precrop_iters and --precrop_frac above are
+    # read by its loop
+    ('--i_testset', dict(type=int, default=2000)), ('--i_video', dict(type=int, default=10000)),
+    ('--select_pixel_mode', dict(type=str, default='rand_pixel', choices=['rand_pixel', 'rand_patch'])),
     # this front-end's own knobs
     # auto (default): fp16_fp8 (fp16 MFMA pass + bf6 correction terms, 1.7x the speed) when the checkpoint's own activation
     # ranges, measured on every ray of the first frame and watched on every frame after it, keep it inside the 1e-4 rgb
@@ -743,7 +747,7 @@ def main(argv=None):
     if not args.render_only:
         if args.model_name not in ('R2L', 'nerf_v3.2'):
             raise SystemExit(f'--model_name {args.model_name} without --render_only: teacher training is not built (the student trains: '
-                             f'--model_name R2L --data_mode rays --datadir_kd DIR)')
+                             f'--model_name R2L --data_mode rays --datadir_kd DIR) into main.py: train_teacher.py takes the same flags')
         if args.data_mode != 'rays' or not args.datadir_kd:
             raise SystemExit('without --render_only main.py trains the student, which is built for ray shards: pass --data_mode rays '
                              '--datadir_kd DIR (or --render_only --pretrained_ckpt X.tar to render)')

@@ -56,7 +56,88 @@ def init_state_dict(plan, seed=None):
     return sd
 
 
-class R2LTrainer:
+class FlatAdam:
+    """What R2LTrainer and train_teacher.NeRFTrainer share: every parameter in one flat device buffer (_param; _grad, _m, _v
+    likewise) cut into per-tensor views by _slices (name -> (offset, count, shape), in the reference's model.parameters() order),
+    one r2l_train_adam launch over the whole buffer, and the state in torch.optim.Adam's format.
+
+    _frozen: names that never receive a gradient (a module the reference builds and its forward never calls).  torch's Adam skips a
+    parameter whose .grad is None: it keeps no state for it and never moves it.  Here their gradient stays zero, which the launch
+    maps to an update of exactly zero with zero moments; the saved state has no entry for them and a loaded state need not."""
+    _frozen = frozenset()
+
+    def _views(self, flat):
+        return OrderedDict((k, flat[o:o + c].view(shape)) for k, (o, c, shape) in self._slices.items())
+
+    def grads(self):
+        self._need_state()
+        return OrderedDict((k, v.detach().clone()) for k, v in self.g.items())
+
+    def _need_state(self):
+        if self._param is None:
+            raise R2LError('the trainer has no weights yet: load_state_dict first')
+
+    def optimizer_state_dict(self):
+        """torch.optim.Adam.state_dict(): parameters indexed in model.parameters() order (weight then bias, layer by layer)."""
+        self._need_state()
+        idx = list(range(len(self._slices)))
+        state = {}
+        if self.t > 0:
+            for i, k in enumerate(self._slices):
+                if k in self._frozen:
+                    continue
+                state[i] = {'step': torch.tensor(float(self.t)), 'exp_avg': self.exp_avg[k].detach().cpu().clone(),
+                            'exp_avg_sq': self.exp_avg_sq[k].detach().cpu().clone()}
+        group = {'lr': float(self.lr), 'betas': ADAM_BETAS, 'eps': ADAM_EPS, 'weight_decay': 0, 'amsgrad': False, 'maximize': False,
+                 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None, 'decoupled_weight_decay': False,
+                 'params': idx}
+        return {'state': state, 'param_groups': [group]}
+
+    def load_optimizer_state_dict(self, osd):
+        self._need_state()
+        groups = osd.get('param_groups', [])
+        n_par = sum(len(g['params']) for g in groups)
+        if n_par != len(self._slices):
+            raise R2LError(f'the optimizer state describes {n_par} parameters, this network has {len(self._slices)}')
+        for g in groups:
+            if tuple(g.get('betas', ADAM_BETAS)) != ADAM_BETAS or g.get('eps', ADAM_EPS) != ADAM_EPS or g.get('weight_decay', 0) != 0 \
+                    or g.get('amsgrad', False):
+                raise R2LError(f"the Adam built here has betas {ADAM_BETAS}, eps {ADAM_EPS}, no weight decay, no amsgrad; the state has "
+                               f"betas {g.get('betas')} eps {g.get('eps')} weight_decay {g.get('weight_decay')} amsgrad {g.get('amsgrad')}")
+        order = [i for g in groups for i in g['params']]
+        state = osd.get('state', {})
+        self._m.zero_()
+        self._v.zero_()
+        steps = set()
+        for pos, k in zip(order, self._slices):
+            st = state.get(pos)
+            if st is None:
+                continue
+            for name, dst in (('exp_avg', self.exp_avg[k]), ('exp_avg_sq', self.exp_avg_sq[k])):
+                if tuple(st[name].shape) != tuple(dst.shape):
+                    raise R2LError(f'optimizer state {pos} ({k}) {name} is {tuple(st[name].shape)}, expected {tuple(dst.shape)}')
+                dst.copy_(st[name].detach().to(torch.float32))
+            steps.add(int(float(st['step'])))
+        n_live = len(self._slices) - len(self._frozen)
+        if len(steps) > 1 or (steps and not n_live <= len(state) <= len(self._slices)):
+            raise R2LError(f'the optimizer state carries step counts {sorted(steps)} over {len(state)} of {n_live} trained parameters: '
+                           f'one flat Adam launch needs one count for all of them')
+        self.t = steps.pop() if steps else 0
+        if groups:
+            self.lr = float(groups[0].get('lr', self.lr))
+        return self
+
+    def adam(self, lr):
+        """One torch.optim.Adam update of every parameter from the gradients in the buffer."""
+        self._need_state()
+        self.t += 1
+        self.lr = float(lr)
+        with torch.cuda.device(self.device):
+            check(lib().r2l_train_adam(dptr(self._param), dptr(self._grad), dptr(self._m), dptr(self._v), self.n_param, float(lr), self.t,
+                                       current_stream()))
+
+
+class R2LTrainer(FlatAdam):
     """NeRF_v3_2 + PointSampler + PositionalEmbedder + MSE loss + torch.optim.Adam(betas (0.9, 0.999)) on the device.
 
     max_rays: the largest batch a step may carry (the buffers are allocated once, at load_state_dict)."""
@@ -115,9 +196,6 @@ class R2LTrainer:
         n = self.max_rays if n is None else n
         return 4 * n * (sum(p['out_dim'] for p in self.plan) + self.input_dim + 4 * self.n_sample)
 
-    def _views(self, flat):
-        return OrderedDict((k, flat[o:o + c].view(shape)) for k, (o, c, shape) in self._slices.items())
-
     def _allocate(self):
         n, dev = self.max_rays, self.device
         f32 = dict(dtype=torch.float32, device=dev)
@@ -164,61 +242,6 @@ class R2LTrainer:
         """The weights on the host, keyed as the reference's network_fn_state_dict."""
         self._need_state()
         return OrderedDict((k, v.detach().cpu().clone()) for k, v in self.p.items())
-
-    def grads(self):
-        self._need_state()
-        return OrderedDict((k, v.detach().clone()) for k, v in self.g.items())
-
-    def _need_state(self):
-        if self._param is None:
-            raise R2LError('the trainer has no weights yet: load_state_dict first')
-
-    def optimizer_state_dict(self):
-        """torch.optim.Adam.state_dict(): parameters indexed in model.parameters() order (weight then bias, layer by layer)."""
-        self._need_state()
-        idx = list(range(len(self._slices)))
-        state = {}
-        if self.t > 0:
-            for i, k in enumerate(self._slices):
-                state[i] = {'step': torch.tensor(float(self.t)), 'exp_avg': self.exp_avg[k].detach().cpu().clone(),
-                            'exp_avg_sq': self.exp_avg_sq[k].detach().cpu().clone()}
-        group = {'lr': float(self.lr), 'betas': ADAM_BETAS, 'eps': ADAM_EPS, 'weight_decay': 0, 'amsgrad': False, 'maximize': False,
-                 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None, 'decoupled_weight_decay': False,
-                 'params': idx}
-        return {'state': state, 'param_groups': [group]}
-
-    def load_optimizer_state_dict(self, osd):
-        self._need_state()
-        groups = osd.get('param_groups', [])
-        n_par = sum(len(g['params']) for g in groups)
-        if n_par != len(self._slices):
-            raise R2LError(f'the optimizer state describes {n_par} parameters, this network has {len(self._slices)}')
-        for g in groups:
-            if tuple(g.get('betas', ADAM_BETAS)) != ADAM_BETAS or g.get('eps', ADAM_EPS) != ADAM_EPS or g.get('weight_decay', 0) != 0 \
-                    or g.get('amsgrad', False):
-                raise R2LError(f"the Adam built here has betas {ADAM_BETAS}, eps {ADAM_EPS}, no weight decay, no amsgrad; the state has "
-                               f"betas {g.get('betas')} eps {g.get('eps')} weight_decay {g.get('weight_decay')} amsgrad {g.get('amsgrad')}")
-        order = [i for g in groups for i in g['params']]
-        state = osd.get('state', {})
-        self._m.zero_()
-        self._v.zero_()
-        steps = set()
-        for pos, k in zip(order, self._slices):
-            st = state.get(pos)
-            if st is None:
-                continue
-            for name, dst in (('exp_avg', self.exp_avg[k]), ('exp_avg_sq', self.exp_avg_sq[k])):
-                if tuple(st[name].shape) != tuple(dst.shape):
-                    raise R2LError(f'optimizer state {pos} ({k}) {name} is {tuple(st[name].shape)}, expected {tuple(dst.shape)}')
-                dst.copy_(st[name].detach().to(torch.float32))
-            steps.add(int(float(st['step'])))
-        if len(steps) > 1 or (steps and len(state) != len(self._slices)):
-            raise R2LError(f'the optimizer state carries step counts {sorted(steps)} over {len(state)} of {len(self._slices)} parameters: '
-                           f'one flat Adam launch needs one count for all of them')
-        self.t = steps.pop() if steps else 0
-        if groups:
-            self.lr = float(groups[0].get('lr', self.lr))
-        return self
 
     # ---- one step ----------------------------------------------------------------------------------------------------------
     def _forward_layer(self, i, x, y, res=None, post=None):
@@ -349,15 +372,6 @@ class R2LTrainer:
             self._grad_weight(0, z, emb)
         return self._loss
 
-    def adam(self, lr):
-        """One torch.optim.Adam update of every parameter from the gradients in the buffer."""
-        self._need_state()
-        self.t += 1
-        self.lr = float(lr)
-        with torch.cuda.device(self.device):
-            check(lib().r2l_train_adam(dptr(self._param), dptr(self._grad), dptr(self._m), dptr(self._v), self.n_param, float(lr), self.t,
-                                       current_stream()))
-
     def step(self, rays_o, rays_d, target, lr, perturb=1., t_rand=None):
         """forward_backward + Adam.  Returns (loss [1], err [n]): views of the trainer's buffers, valid until the next step;
         err[r] = mean over the channels of (rgb - target)^2 from this step's forward pass (what the hard-ray pool sorts)."""
@@ -452,8 +466,15 @@ def _infinite_order(n):
 def save_train_checkpoint(path, trainer, global_step, best_psnr=0, best_psnr_step=0):
     """The reference's schema (main.py:1516-1542) with the optimizer's state; without the pickled module, which the reference
     only reads when it is there (main.py:484)."""
+    fine = None
+    if hasattr(trainer, 'state_dicts'):        # the teacher's pair: network_fine_state_dict beside it (main.py:1531-1533)
+        coarse, fine = trainer.state_dicts()
+    else:
+        coarse = trainer.state_dict()
     to_save = {'global_step': int(global_step), 'best_psnr': best_psnr, 'best_psnr_step': best_psnr_step,
-               'network_fn_state_dict': dict(trainer.state_dict()), 'optimizer_state_dict': trainer.optimizer_state_dict()}
+               'network_fn_state_dict': dict(coarse), 'optimizer_state_dict': trainer.optimizer_state_dict()}
+    if fine is not None:
+        to_save['network_fine_state_dict'] = dict(fine)
     tmp = path + '.tmp'
     torch.save(to_save, tmp)
     os.replace(tmp, path)

@@ -1,0 +1,617 @@
+"""Training of the NeRF teacher (main.py:1136-1513 with --model_name nerf, --data_mode images, no_batching; the step is
+render_rays, main.py:624-756, under autograd plus torch.optim.Adam): both networks' forward and backward passes, both
+volume-rendering scans and their backward pass, the two rgb losses and Adam as launches of the library's fp32 kernels
+(csrc/r2l_generic.hip, r2l_train.hip, nerf_kernels.hip, nerf_train.hip; include/r2l_hip.h).
+
+NeRFTrainer holds the coarse network's parameters, then the fine one's, in one flat device buffer (train.FlatAdam), and the
+saved output of every layer of both passes for the backward pass.  torch supplies the buffers, the stream and the random draws
+(t_rand, u, the density noise); every number of a step is computed by the library in exact fp32, and a step is bit-identical from
+run to run (no float atomics anywhere).
+
+The networks are generic.nerf_plan's: every pair create_nerf builds (main.py:407-453).  The reference's two torch.cat inputs are
+column slices of wider buffers, as in generic._NeRFNet.forward.
+"""
+import math
+import os
+import time
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from ._lib import R2LError, check, current_stream, dptr, lib
+from .generic import _strip, _view, nerf_plan
+from .train import FlatAdam, jitter_z_vals, learning_rate, save_train_checkpoint
+
+ACT_NONE, ACT_RELU = 0, 1
+SKIPS = (4,)
+PREFIXES = ('network_fn', 'network_fine')
+
+
+def reference_order(D, W, input_ch, input_ch_views, output_ch, use_viewdirs):
+    """(key, in_dim, out_dim) of one NeRF in the order its constructor creates the modules (model/nerf_raybased.py:357-375), which
+    is model.parameters() order and so the optimizer's: pts_linears.*, views_linears.0 (always built), then feature_linear,
+    alpha_linear, rgb_linear -- or output_linear.  generic.nerf_plan lists the same layers in execution order."""
+    plan = {k: (i, o) for k, i, o in nerf_plan(D, W, input_ch, input_ch_views, output_ch, SKIPS, use_viewdirs)}
+    keys = [f'pts_linears.{i}' for i in range(D)] + ['views_linears.0']
+    keys += ['feature_linear', 'alpha_linear', 'rgb_linear'] if use_viewdirs else ['output_linear']
+    plan.setdefault('views_linears.0', (input_ch_views + W, W // 2))
+    return [(k,) + plan[k] for k in keys]
+
+
+class _Net:
+    """Shapes and per-step buffers of one of the two networks"""
+
+    def __init__(self, prefix, D, W, S):
+        self.prefix, self.D, self.W, self.S = prefix, D, W, S
+
+
+class NeRFTrainer(FlatAdam):
+    """render_rays (main.py:624-756) of a batch of rays + img2mse(rgb) + img2mse(rgb0) + their gradients + torch.optim.Adam(betas
+    (0.9, 0.999)) over list(model.parameters()) + list(model_fine.parameters()) (main.py:425-445), on the device.
+
+    Parameter names carry the network's checkpoint key: network_fn.pts_linears.0.weight, ..., network_fine.rgb_linear.bias.
+    Without use_viewdirs the reference still builds views_linears.0 and never calls it: it is in the state dict, its gradient stays
+    zero and Adam leaves it as it is (FlatAdam._frozen); the saved optimizer state has no entry under its two indices, as torch's
+    has none for a parameter whose .grad is None, and a state with or without such entries loads.
+
+    max_rays: the largest batch a step may carry (the buffers are allocated once, at load_state_dicts)."""
+
+    def __init__(self, near=2., far=6., N_samples=64, N_importance=128, multires=10, multires_views=4, i_embed=0, netdepth=8,
+                 netwidth=256, netdepth_fine=8, netwidth_fine=256, use_viewdirs=True, white_bkgd=False, lindisp=False,
+                 max_rays=1024, device=None):
+        if not torch.cuda.is_available():
+            raise R2LError('no HIP device visible to torch: training has no CPU fallback')
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.near, self.far = float(near), float(far)
+        self.N_samples, self.N_importance = int(N_samples), int(N_importance)
+        self.multires, self.multires_views, self.i_embed = int(multires), int(multires_views), int(i_embed)
+        if self.i_embed not in (0, -1):
+            raise R2LError(f'i_embed={i_embed}: 0 (positional encoding) or -1 (none), utils/run_nerf_raybased_helpers.py:59-74')
+        if self.N_samples < 1 or self.N_importance < 0 or (self.N_importance > 0 and not 3 <= self.N_samples <= 65):
+            raise R2LError(f'N_samples={N_samples} N_importance={N_importance}: sample_pdf takes 2 .. 64 bins (N_samples - 1 of them)')
+        self.use_viewdirs, self.white_bkgd, self.lindisp = bool(use_viewdirs), bool(white_bkgd), bool(lindisp)
+        self.input_ch = 3 if self.i_embed == -1 else 3 * (2 * self.multires + 1)
+        self.input_ch_views = 0 if not self.use_viewdirs else (3 if self.i_embed == -1 else 3 * (2 * self.multires_views + 1))
+        self.output_ch = 5 if self.N_importance > 0 else 4          # main.py:426
+        self.raw_ch = 4 if self.use_viewdirs else self.output_ch
+        self.max_rays = int(max_rays)
+        if self.max_rays < 1:
+            raise R2LError(f'max_rays={max_rays}')
+        self.nets = [_Net(PREFIXES[0], int(netdepth), int(netwidth), self.N_samples)]
+        if self.N_importance > 0:
+            self.nets.append(_Net(PREFIXES[1], int(netdepth_fine), int(netwidth_fine), self.N_samples + self.N_importance))
+        for net in self.nets:
+            if net.D < 1 or net.W < 2:
+                raise R2LError(f'{net.prefix}: netdepth {net.D} netwidth {net.W}')
+            if (net.D - 1) in SKIPS:
+                raise R2LError(f'{net.prefix}: netdepth {net.D} makes the last pts_linears layer a skip layer: alpha_linear / feature_linear '
+                               f'take W inputs (the reference fails too)')
+            net.layers = OrderedDict((k, (i, o)) for k, i, o in reference_order(net.D, net.W, self.input_ch, self.input_ch_views,
+                                                                                 self.output_ch, self.use_viewdirs))
+        # main.py:676-682 on the host as the reference's first ray computes it (near, far are the same for every ray)
+        t = torch.linspace(0., 1., steps=self.N_samples)
+        nr, fr = torch.tensor([self.near]), torch.tensor([self.far])
+        z = nr * (1. - t) + fr * t if not self.lindisp else 1. / (1. / nr * (1. - t) + 1. / fr * t)
+        self.z_coarse = z.to(torch.float32).contiguous()
+        # flat layout: the coarse network, then the fine one; weight then bias, module by module in creation order
+        self._slices = OrderedDict()
+        off = 0
+        for net in self.nets:
+            for k, (i, o) in net.layers.items():
+                for kind, shape in (('weight', (o, i)), ('bias', (o,))):
+                    cnt = int(np.prod(shape))
+                    self._slices[f'{net.prefix}.{k}.{kind}'] = (off, cnt, shape)
+                    off += cnt
+        self.n_param = off
+        if not self.use_viewdirs:
+            self._frozen = frozenset(f'{net.prefix}.views_linears.0.{kind}' for net in self.nets for kind in ('weight', 'bias'))
+        self.t = 0
+        self.lr = 0.
+        self._param = None
+        self.last = {}
+
+    # ---- state -------------------------------------------------------------------------------------------------------------
+    @property
+    def flops_per_ray(self):
+        """of the two forward passes; a training step is about three times that (g_x and g_W cost one forward each)"""
+        return 2 * sum(net.S * sum(i * o for k, (i, o) in net.layers.items() if self.use_viewdirs or k != 'views_linears.0')
+                       for net in self.nets)
+
+    def state_names(self):
+        return list(self._slices)
+
+    def _per_point_floats(self, net):
+        """saved layer outputs and inputs of one point of one network"""
+        ic, icv, W = self.input_ch, self.input_ch_views, net.W
+        return 3 + (ic + W) + (W + icv + W // 2 if self.use_viewdirs else 0) + W * sum(1 for i in range(net.D) if i not in SKIPS) + self.raw_ch + 4
+
+    def activation_bytes(self, n=None):
+        n = self.max_rays if n is None else n
+        return 4 * n * sum(net.S * self._per_point_floats(net) for net in self.nets)
+
+    def _allocate(self):
+        n, dev = self.max_rays, self.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        ic, icv = self.input_ch, self.input_ch_views
+        m_max = n * max(net.S for net in self.nets)
+        w_max = max(net.W for net in self.nets)
+        slabs = lib().r2l_train_grad_weight_slabs(m_max)
+        ws_floats = max(1, slabs * max(i * o + o for net in self.nets for i, o in net.layers.values()))
+        grad_floats = m_max * (2 * (ic + w_max) + w_max + (w_max + icv + w_max) + 4 + self.raw_ch)
+        want = self.activation_bytes() + 4 * (4 * self.n_param + grad_floats + ws_floats)
+        sizes = (f'about {want / 2 ** 30:.1f} GiB (saved layer outputs {self.activation_bytes() / 2 ** 30:.1f} GiB: ' +
+                 ', '.join(f'{net.prefix} {n * net.S} points x {self._per_point_floats(net)} floats' for net in self.nets) +
+                 f'; gradient buffers {4 * grad_floats / 2 ** 30:.1f} GiB; slab workspace {4 * ws_floats / 2 ** 30:.2f} GiB)')
+        free = torch.cuda.mem_get_info(dev)[0]
+        if want > free:               # before anything is allocated: a step that cannot fit leaves the device as it found it
+            raise R2LError(f'the training buffers for {n} rays per step need {sizes}; the device has {free / 2 ** 30:.1f} GiB free. '
+                           f'Lower --N_rand.')
+        try:
+            with torch.cuda.device(dev):
+                self._param, self._grad, self._m, self._v = (torch.zeros(self.n_param, **f32) for _ in range(4))
+                for net in self.nets:
+                    m, W = n * net.S, net.W
+                    net.pts = torch.empty((m, 3), **f32)
+                    net.cat = torch.empty((m, ic + W), **f32)
+                    net.views = torch.empty((m, W + icv), **f32) if self.use_viewdirs else None
+                    net.hv = torch.empty((m, W // 2), **f32) if self.use_viewdirs else None
+                    net.acts = [None if i in SKIPS else torch.empty((m, W), **f32) for i in range(net.D)]
+                    net.raw = torch.empty((m, self.raw_ch), **f32)
+                    net.raw4 = net.raw if self.raw_ch == 4 else torch.empty((m, 4), **f32)
+                    net.rgb = torch.empty((n, 3), **f32)
+                    net.g_rgb = torch.empty((n, 3), **f32)
+                    net.loss = torch.zeros((1,), **f32)
+                # gradient work buffers, shared by the two backward passes (they run one after the other on one stream)
+                self._GA, self._GB = (torch.empty((m_max * (ic + w_max),), **f32) for _ in range(2))
+                self._Z = torch.empty((m_max * w_max,), **f32)
+                self._gviews = torch.empty((m_max * (w_max + icv),), **f32) if self.use_viewdirs else None
+                self._ghv, self._gzv = ((torch.empty((m_max * (w_max // 2),), **f32) for _ in range(2)) if self.use_viewdirs else (None, None))
+                self._g_raw = torch.empty((m_max * 4,), **f32)
+                self._g_out = torch.zeros((m_max * self.raw_ch,), **f32) if self.raw_ch != 4 else None
+                self._err = torch.empty((n,), **f32)
+                self._ws = torch.empty((ws_floats,), **f32)
+                self._loss_ws = torch.empty(((n + 255) // 256,), **f32)
+                self._scan = [torch.empty((n,), **f32) for _ in range(3)]              # disp, acc, depth: computed, not trained on
+                self._weights = torch.empty((n, self.N_samples), **f32)
+                self._z_dev = self.z_coarse.to(dev)
+        except (torch.cuda.OutOfMemoryError, RuntimeError) as e:
+            self._param = None
+            for net in self.nets:
+                net.__dict__ = {k: v for k, v in net.__dict__.items() if not torch.is_tensor(v) and k != 'acts'}
+            raise R2LError(f'cannot allocate the training buffers for {n} rays per step: {sizes}: {e}. Lower --N_rand.') from e
+        self.p, self.g = self._views(self._param), self._views(self._grad)
+        self.exp_avg, self.exp_avg_sq = self._views(self._m), self._views(self._v)
+
+    def init_state_dicts(self, seed=None):
+        """nn.Linear's default initialisation of every module, in creation order: (coarse, fine or None)"""
+        g = torch.random.get_rng_state()
+        if seed is not None:
+            torch.manual_seed(seed)
+        out = []
+        for net in self.nets:
+            sd = OrderedDict()
+            for k, (i, o) in net.layers.items():
+                lin = torch.nn.Linear(i, o)
+                sd[k + '.weight'], sd[k + '.bias'] = lin.weight.detach().clone(), lin.bias.detach().clone()
+            out.append(sd)
+        if seed is not None:
+            torch.random.set_rng_state(g)
+        return out[0], (out[1] if len(out) > 1 else None)
+
+    def load_state_dicts(self, network_fn_state_dict, network_fine_state_dict=None):
+        sds = [_strip(network_fn_state_dict)]
+        if self.N_importance > 0:
+            if network_fine_state_dict is None:
+                raise R2LError('N_importance > 0 needs network_fine_state_dict (main.py:436-445)')
+            sds.append(_strip(network_fine_state_dict))
+        for net, sd in zip(self.nets, sds):
+            for k, (i, o) in net.layers.items():
+                for kind, shape in (('weight', (o, i)), ('bias', (o,))):
+                    if f'{k}.{kind}' not in sd:
+                        raise R2LError(f'{net.prefix}_state_dict lacks {k}.{kind} (has e.g. {sorted(sd)[:4]})')
+                    if tuple(sd[f'{k}.{kind}'].shape) != shape:
+                        raise R2LError(f'{net.prefix}: {k}.{kind} is {tuple(sd[f"{k}.{kind}"].shape)}, the flags describe {shape}')
+        if self._param is None:
+            self._allocate()
+        for net, sd in zip(self.nets, sds):
+            for k in net.layers:
+                for kind in ('weight', 'bias'):
+                    self.p[f'{net.prefix}.{k}.{kind}'].copy_(torch.as_tensor(sd[f'{k}.{kind}']).detach().to(torch.float32))
+        return self
+
+    def _split(self, views, host):
+        out = []
+        for net in self.nets:
+            cut = len(net.prefix) + 1
+            out.append(OrderedDict((k[cut:], (v.detach().cpu().clone() if host else v.detach().clone())) for k, v in views.items()
+                                   if k.startswith(net.prefix + '.')))
+        return out[0], (out[1] if len(out) > 1 else None)
+
+    def state_dicts(self):
+        """(network_fn_state_dict, network_fine_state_dict or None) on the host, keyed as the reference's checkpoint"""
+        self._need_state()
+        return self._split(self.p, True)
+
+    def grads(self):
+        """the gradients of the last forward_backward, as state_dicts() is keyed: (coarse, fine or None), on the device"""
+        self._need_state()
+        return self._split(self.g, False)
+
+    # ---- launches ----------------------------------------------------------------------------------------------------------
+    def _w(self, net, key):
+        return self.p[f'{net.prefix}.{key}.weight'], self.p[f'{net.prefix}.{key}.bias']
+
+    def _linear(self, net, key, x, y, act):
+        i, o = net.layers[key]
+        w, b = self._w(net, key)
+        xp, ldx = _view(x, i)
+        yp, ldy = _view(y, o)
+        check(lib().r2l_linear_forward_dev(dptr(w), dptr(b), o, i, xp, ldx, x.shape[0], yp, ldy, None, 0, 1.0, act, None, 0,
+                                           current_stream()))
+
+    def _grad_weight(self, net, key, gz, x):
+        i, o = net.layers[key]
+        zp, ldz = _view(gz, o)
+        xp, ldx = _view(x, i)
+        check(lib().r2l_train_grad_weight(zp, ldz, xp, ldx, x.shape[0], o, i, dptr(self.g[f'{net.prefix}.{key}.weight']),
+                                          dptr(self.g[f'{net.prefix}.{key}.bias']), dptr(self._ws), self._ws.numel(), current_stream()))
+
+    def _grad_input(self, net, key, gz, gx, accumulate):
+        i, o = net.layers[key]
+        zp, ldz = _view(gz, o)
+        xp, ldx = _view(gx, i)
+        check(lib().r2l_train_grad_input(zp, ldz, gz.shape[0], dptr(self._w(net, key)[0]), o, i, xp, ldx, 1 if accumulate else 0,
+                                         current_stream()))
+
+    def _relu_backward(self, g_y, y, g_z):
+        w = y.shape[1]
+        gp, ldg = _view(g_y, w)
+        yp, ldy = _view(y, w)
+        zp, ldz = _view(g_z, w)
+        check(lib().r2l_train_act_backward(gp, ldg, yp, ldy, None, 0, y.shape[0], w, ACT_RELU, 1.0, zp, ldz, None, 0, 0, None, 0, 0,
+                                           current_stream()))
+
+    def _embed(self, x, L, out):
+        """get_embedder(L, i_embed) of x [m, 3] into the view `out`"""
+        if self.i_embed == -1:
+            out.copy_(x)
+            return
+        op, ldo = _view(out)
+        check(lib().nerf_embed(dptr(x), 3, x.shape[0], 3, L, op, ldo, current_stream()))
+
+    def _layer_io(self, net, m):
+        """per pts_linears layer: (input view, output view) over the first m points"""
+        ic = self.input_ch
+        cat = net.cat[:m]
+        io, x = [], cat[:, :ic]
+        for i in range(net.D):
+            y = cat[:, ic:] if i in SKIPS else net.acts[i][:m]
+            io.append((x, y))
+            x = cat if i in SKIPS else y
+        return io
+
+    def _net_forward(self, net, ro, rd, viewdirs, z):
+        """network_query_fn(rays_o + rays_d * z, viewdirs, network) (main.py:65-87, 701-707) keeping every layer's output:
+        raw [n * S, raw_ch] (a view)"""
+        n, S, W, ic = ro.shape[0], net.S, net.W, self.input_ch
+        m = n * S
+        pts, cat, raw = net.pts[:m], net.cat[:m], net.raw[:m]
+        check(lib().r2l_sample_points(dptr(ro), dptr(rd), n, dptr(z), S, 1, dptr(pts), current_stream()))
+        self._embed(pts, self.multires, cat[:, :ic])
+        io = self._layer_io(net, m)
+        for i, (x, y) in enumerate(io):
+            self._linear(net, f'pts_linears.{i}', x, y, ACT_RELU)
+        h = io[-1][1]
+        if not self.use_viewdirs:
+            self._linear(net, 'output_linear', h, raw, ACT_NONE)
+            return raw
+        views, hv = net.views[:m], net.hv[:m]
+        dirs = viewdirs[:, None, :].expand(n, S, 3).reshape(m, 3).contiguous()        # main.py:76-77
+        self._embed(dirs, self.multires_views, views[:, W:])
+        self._linear(net, 'alpha_linear', h, raw[:, 3:4], ACT_NONE)
+        self._linear(net, 'feature_linear', h, views[:, :W], ACT_NONE)
+        self._linear(net, 'views_linears.0', views, hv, ACT_RELU)
+        self._linear(net, 'rgb_linear', hv, raw[:, :3], ACT_NONE)
+        return raw
+
+    def _scan_forward(self, net, raw, z, rd, noise, weights):
+        """raw2outputs (main.py:556-621): rgb_map into net.rgb; returns the [n, S, 4] block the scan read"""
+        n, S = rd.shape[0], net.S
+        raw4 = net.raw4[:n * S]
+        if raw4.data_ptr() != raw.data_ptr():
+            raw4.copy_(raw[:, :4])                    # raw2outputs reads channels 0..3 (main.py:588-600); the fifth is never used
+        disp, acc, depth = (b[:n] for b in self._scan)
+        check(lib().nerf_raw2outputs_noise(dptr(raw4), dptr(z), dptr(rd), dptr(noise), n, S, int(self.white_bkgd), dptr(net.rgb[:n]),
+                                           dptr(disp), dptr(acc), dptr(weights), dptr(depth), current_stream()))
+        return raw4
+
+    def _scan_backward(self, net, raw4, z, rd, noise, g_raw):
+        """g_raw [n * S, 4] from net.g_rgb (csrc/nerf_train.hip)"""
+        n = rd.shape[0]
+        check(lib().nerf_train_raw2outputs_backward(dptr(raw4), dptr(z), dptr(rd), dptr(noise), n, net.S, int(self.white_bkgd),
+                                                    dptr(net.g_rgb[:n]), dptr(g_raw), current_stream()))
+        return g_raw
+
+    def _net_backward(self, net, raw4, z, rd, noise, n):
+        """from net.g_rgb (the loss's gradient at rgb_map) through the scan and the network into the flat gradient buffer"""
+        S, W, ic = net.S, net.W, self.input_ch
+        m = n * S
+        mat = lambda flat, cols: flat[:m * cols].view(m, cols)
+        g_raw = self._scan_backward(net, raw4, z, rd, noise, mat(self._g_raw, 4))
+        io = self._layer_io(net, m)
+        h = io[-1][1]
+        g_h = mat(self._GA, W)
+        if self.use_viewdirs:
+            views, hv = net.views[:m], net.hv[:m]
+            g_hv, g_zv, g_views = mat(self._ghv, W // 2), mat(self._gzv, W // 2), mat(self._gviews, W + self.input_ch_views)
+            self._grad_weight(net, 'rgb_linear', g_raw[:, :3], hv)
+            self._grad_input(net, 'rgb_linear', g_raw[:, :3], g_hv, False)
+            self._relu_backward(g_hv, hv, g_zv)
+            self._grad_weight(net, 'views_linears.0', g_zv, views)
+            self._grad_input(net, 'views_linears.0', g_zv, g_views, False)
+            self._grad_weight(net, 'feature_linear', g_views[:, :W], h)
+            self._grad_input(net, 'feature_linear', g_views[:, :W], g_h, False)
+            self._grad_weight(net, 'alpha_linear', g_raw[:, 3:4], h)             # alpha and feature both read h: their g_h add up
+            self._grad_input(net, 'alpha_linear', g_raw[:, 3:4], g_h, True)
+        else:
+            g_out = g_raw
+            if self.raw_ch != 4:                      # the unused fifth output: its column of g_out stays zero
+                g_out = mat(self._g_out, self.raw_ch)
+                g_out[:, :4].copy_(g_raw)
+            self._grad_weight(net, 'output_linear', g_out, h)
+            self._grad_input(net, 'output_linear', g_out, g_h, False)
+        g_y, cur, other = g_h, self._GA, self._GB
+        g_z = mat(self._Z, W)
+        for i in range(net.D - 1, -1, -1):
+            x, y = io[i]
+            self._relu_backward(g_y, y, g_z)
+            self._grad_weight(net, f'pts_linears.{i}', g_z, x)
+            if i > 0:                                 # the embedding has no parameters: no g_x for layer 0
+                g_x = mat(other, x.shape[1])
+                self._grad_input(net, f'pts_linears.{i}', g_z, g_x, False)
+                g_y = g_x[:, ic:] if (i - 1) in SKIPS else g_x     # behind a skip layer x = [input_pts | h]
+                cur, other = other, cur
+
+    # ---- one step ----------------------------------------------------------------------------------------------------------
+    def _draw(self, given, shape, what, scale=None):
+        if given is None:
+            t = torch.rand(shape, dtype=torch.float32, device=self.device) if scale is None else \
+                torch.randn(shape, dtype=torch.float32, device=self.device) * scale
+            return t
+        t = given.to(self.device, torch.float32).contiguous()
+        if tuple(t.shape) != tuple(shape):
+            raise R2LError(f'{what} is {tuple(t.shape)}, expected {tuple(shape)}')
+        return t
+
+    def forward_backward(self, rays_o, rays_d, target, perturb=1., raw_noise_std=0., t_rand=None, u=None, noise=None):
+        """loss = img2mse(rgb, target) + img2mse(rgb0, target) (a one-element device tensor; the coarse term alone with
+        N_importance = 0); the gradients are left in the flat buffer (grads()).
+
+        t_rand [n, N_samples], u [n, N_importance] in [0, 1) and noise = (noise0 [n, N_samples], noise1 [n, N_samples +
+        N_importance]) (what is added to the density in front of its relu: randn * raw_noise_std) replace the draws of main.py:691,
+        helpers:298-307 and main.py:592-598; by default they are torch draws on the device.  self.last keeps the step's detached
+        quantities: per pass the embedded inputs (`emb0`, `emb1`: [n * S, input_ch]; `dirs0`, `dirs1`: the embedded view
+        directions), the depths (`z0`, `z1`), the noise, `raw0` / `raw1`, and `rgb0` / `rgb`."""
+        from .teacher import merge_sorted, sample_pdf
+        self._need_state()
+        n = rays_o.shape[0]
+        if n > self.max_rays or n < 1:
+            raise R2LError(f'{n} rays in a step, the buffers were allocated for max_rays = {self.max_rays}')
+        dev = self.device
+        ro = rays_o.to(dev, torch.float32).contiguous()
+        rd = rays_d.to(dev, torch.float32).contiguous()
+        tgt = target.to(dev, torch.float32).contiguous()
+        if tuple(ro.shape) != (n, 3) or tuple(rd.shape) != (n, 3) or tuple(tgt.shape) != (n, 3):
+            raise R2LError(f'rays_o / rays_d / target are {tuple(ro.shape)} / {tuple(rd.shape)} / {tuple(tgt.shape)}, expected {(n, 3)}')
+        S0, Ni = self.N_samples, self.N_importance
+        fine = Ni > 0
+        noises = [None, None]
+        if noise is not None or raw_noise_std > 0.:
+            given = noise if noise is not None else (None, None)
+            noises = [self._draw(given[k], (n, net.S), f'noise[{k}]', raw_noise_std) for k, net in enumerate(self.nets)]
+        with torch.cuda.device(dev):
+            viewdirs = rd / torch.norm(rd, dim=-1, keepdim=True) if self.use_viewdirs else None      # main.py:148-157
+            if perturb > 0.:
+                z0 = jitter_z_vals(self._z_dev, n, self._draw(t_rand, (n, S0), 't_rand'))             # main.py:684-699
+            else:
+                z0 = self._z_dev.expand(n, S0).contiguous()
+            c, f = self.nets[0], (self.nets[1] if fine else None)
+            weights = self._weights[:n]
+            raw0 = self._net_forward(c, ro, rd, viewdirs, z0)
+            raw0_4 = self._scan_forward(c, raw0, z0, rd, noises[0], weights)
+            self.last = dict(z0=z0, raw0=raw0, rgb0=c.rgb[:n], noise0=noises[0], emb0=c.cat[:n * S0, :self.input_ch],
+                             dirs0=c.views[:n * S0, c.W:] if self.use_viewdirs else None)
+            if fine:
+                z_mid = .5 * (z0[:, 1:] + z0[:, :-1])                                                 # main.py:722-732
+                z_samples = sample_pdf(z_mid, weights[:, 1:-1], Ni, det=(perturb == 0.),
+                                       u=None if perturb == 0. else self._draw(u, (n, Ni), 'u'))
+                if perturb > 0.:          # drawn u: the samples come out in u's order, and main.py:730-732 is a real sort
+                    z_samples = torch.sort(z_samples, -1)[0]
+                z1 = merge_sorted(z0, z_samples)
+                raw1 = self._net_forward(f, ro, rd, viewdirs, z1)
+                raw1_4 = self._scan_forward(f, raw1, z1, rd, noises[1], None)
+                self.last.update(z1=z1, z_samples=z_samples, raw1=raw1, rgb=f.rgb[:n], noise1=noises[1],
+                                 emb1=f.cat[:n * f.S, :self.input_ch], dirs1=f.views[:n * f.S, f.W:] if self.use_viewdirs else None)
+            else:
+                self.last['rgb'] = c.rgb[:n]
+            top = f if fine else c
+            for net in self.nets:                     # img2mse and its gradient at rgb_map; the per-ray error of the final rgb
+                check(lib().r2l_train_mse_loss(dptr(net.rgb[:n]), dptr(tgt), n, 0, dptr(net.g_rgb[:n]),
+                                               dptr(self._err[:n]) if net is top else None, dptr(net.loss), dptr(self._loss_ws),
+                                               self._loss_ws.numel(), current_stream()))
+            if fine:
+                self._net_backward(f, raw1_4, z1, rd, noises[1], n)
+            self._net_backward(c, raw0_4, z0, rd, noises[0], n)
+            self.loss_rgb = top.loss
+            return c.loss + f.loss if fine else c.loss                                                 # main.py:1362-1380
+
+    def step(self, rays_o, rays_d, target, lr, perturb=1., raw_noise_std=0., t_rand=None, u=None, noise=None):
+        """forward_backward + Adam.  Returns (loss [1], loss_rgb [1]): the sum the gradients are of, and img2mse of the final rgb
+        alone (what the reference's psnr line reports, main.py:1377-1379)."""
+        loss = self.forward_backward(rays_o, rays_d, target, perturb, raw_noise_std, t_rand, u, noise)
+        self.adam(lr)
+        return loss, self.loss_rgb
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the loop of main.py:1136-1513 for --model_name nerf, --data_mode images, no_batching, Blender
+# ---------------------------------------------------------------------------------------------------------------------------
+def crop_bounds(H, W, precrop_frac):
+    """main.py:1270-1278: the centre crop's (row0, rows, col0, cols)"""
+    dH = int(H // 2 * precrop_frac)
+    dW = int(W // 2 * precrop_frac)
+    return H // 2 - dH, 2 * dH, W // 2 - dW, 2 * dW
+
+
+def select_coords(H, W, N_rand, crop=None):
+    """get_selected_coords(coords, N_rand, 'rand_pixel') (utils/run_nerf_raybased_helpers.py:385-392) over the full image or the
+    centre crop of main.py:1270-1287: one np.random.choice(h * w, N_rand, replace=False) of the global numpy stream, row-major
+    over the coords grid.  Returns int64 (rows, cols) [N_rand]."""
+    r0, h, c0, w = (0, H, 0, W) if crop is None else crop
+    if N_rand > h * w:
+        raise R2LError(f'N_rand {N_rand} exceeds the {h} x {w} pixels to choose from')
+    ix = np.random.choice(h * w, size=[N_rand], replace=False)
+    return r0 + ix // w, c0 + ix % w
+
+
+REFUSALS = {
+    'use_batching': 'use_batching (no --no_batching / no_batching = True): teacher training is built for one image per step',
+    'llff': '--dataset_type {}: teacher training is built for Blender scenes (--dataset_type blender)',
+    'rand_patch': '--select_pixel_mode rand_patch: teacher training selects pixels with rand_pixel',
+    'i_video': '--i_video {} falls inside this run: the video render is not built for training; pass an --i_video above --N_iters',
+    'datadir_kd': '--datadir_kd with --data_mode images: pseudo images are not built for teacher training',
+    'data_mode': '--data_mode {}: the teacher trains on images (--data_mode images)',
+    'model_name': '--model_name {}: train_teacher.py trains --model_name nerf (main.py trains the student)',
+}
+
+
+def check_supported(args, start=0):
+    """one clear line for each mode of the reference's loop that is not built"""
+    if args.model_name != 'nerf':
+        raise SystemExit(REFUSALS['model_name'].format(args.model_name))
+    if not args.no_batching:
+        raise SystemExit(REFUSALS['use_batching'])
+    if args.dataset_type != 'blender':
+        raise SystemExit(REFUSALS['llff'].format(args.dataset_type))
+    if args.select_pixel_mode != 'rand_pixel':
+        raise SystemExit(REFUSALS['rand_patch'])
+    if args.data_mode != 'images':
+        raise SystemExit(REFUSALS['data_mode'].format(args.data_mode))
+    if args.datadir_kd:
+        raise SystemExit(REFUSALS['datadir_kd'])
+    if args.i_video > 0 and args.N_iters // args.i_video > start // args.i_video:
+        raise SystemExit(REFUSALS['i_video'].format(args.i_video))
+
+
+def trainer_from_args(args, max_rays):
+    return NeRFTrainer(2., 6., N_samples=args.N_samples, N_importance=args.N_importance, multires=args.multires,       # main.py:930-931
+                       multires_views=args.multires_views, i_embed=args.i_embed, netdepth=args.netdepth, netwidth=args.netwidth,
+                       netdepth_fine=args.netdepth_fine, netwidth_fine=args.netwidth_fine, use_viewdirs=args.use_viewdirs,
+                       white_bkgd=args.white_bkgd, lindisp=args.lindisp, max_rays=max_rays)
+
+
+def eval_test_split(trainer, args, hwf, poses, gt):
+    """render_path over the test split from the current weights (main.py:1442-1456) on generic.GenericNeRF: (test_psnr, test_psnr_v2)"""
+    from .frontend import mse2psnr
+    from .generic import GenericNeRF
+    H, W, focal = hwf
+    eng = GenericNeRF(H, W, focal, 2., 6., N_samples=args.N_samples, N_importance=args.N_importance, multires=args.multires,
+                      multires_views=args.multires_views, i_embed=args.i_embed, netdepth=args.netdepth, netwidth=args.netwidth,
+                      netdepth_fine=args.netdepth_fine, netwidth_fine=args.netwidth_fine, use_viewdirs=args.use_viewdirs,
+                      white_bkgd=args.white_bkgd, lindisp=args.lindisp, device=trainer.device)
+    eng.load_state_dicts(*trainer.state_dicts())
+    mses = []
+    for pose, img in zip(poses, gt):
+        rgb = eng.render(pose[:3, :4])['rgb_map'].view(H, W, 3)
+        mses.append(float(torch.mean((rgb - img.to(rgb.device)) ** 2).item()))
+    return mse2psnr(float(np.mean(mses))), float(np.mean([mse2psnr(m) for m in mses]))
+
+
+def train(args, log=print):
+    """main.py without --render_only for --model_name nerf: returns the path of the last checkpoint"""
+    from . import blender
+    from .frontend import load_checkpoint, mse2psnr
+    from .teacher import get_rays
+    start, ckpt = 0, None
+    if args.pretrained_ckpt:
+        ckpt = load_checkpoint(args.pretrained_ckpt)
+        if args.resume:
+            start = int(ckpt['global_step'])
+    check_supported(args, start)
+    images, poses, hwf, (i_train, i_val, i_test) = blender.load_blender_data(args.datadir, args.half_res, args.testskip)
+    images = blender.composite(images, args.white_bkgd)
+    H, W, focal = int(hwf[0]), int(hwf[1]), float(hwf[2])
+    trainer = trainer_from_args(args, args.N_rand)
+    dev = trainer.device
+    best_psnr, best_psnr_step = 0., 0
+    if ckpt is not None:
+        trainer.load_state_dicts(ckpt['network_fn_state_dict'], ckpt.get('network_fine_state_dict'))
+        log(f'Load pretrained ckpt successfully: "{args.pretrained_ckpt}".')
+        if args.resume:                                       # main.py:504-509
+            trainer.load_optimizer_state_dict(ckpt['optimizer_state_dict'])
+            best_psnr, best_psnr_step = float(ckpt.get('best_psnr', 0.)), int(ckpt.get('best_psnr_step', 0))
+            log('Resume optimizer successfully.')
+    else:
+        trainer.load_state_dicts(*trainer.init_state_dicts())
+    weights_dir = os.path.join(args.basedir, args.expname or 'train_teacher', 'weights')
+    os.makedirs(weights_dir, exist_ok=True)
+    log(f'Loaded blender {tuple(images.shape)} from "{args.datadir}": {len(i_train)} train / {len(i_val)} val / {len(i_test)} test images, '
+        f'{H} x {W}, focal {focal:.4f}; {args.N_rand} rays per step, {args.N_samples} + {args.N_importance} samples; {trainer.n_param} '
+        f'parameters, {trainer.activation_bytes() / 2 ** 30:.2f} GiB of saved activations')
+    crop = crop_bounds(H, W, args.precrop_frac)
+    hist_psnr = 0.
+    path = None
+    log('Begin training')
+    for i in range(start + 1, args.N_iters + 1):
+        t0 = time.time()
+        lr = learning_rate(i, args.lrate, args.lrate_decay, args.warmup_lr)
+        img_i = np.random.choice(i_train)                     # main.py:1213
+        rays_o, rays_d = get_rays(H, W, focal, poses[img_i, :3, :4], device=dev)
+        cropped = i < args.precrop_iters
+        if cropped and i == start + 1:
+            log(f'[Config] Center cropping of size {crop[1]} x {crop[3]} is enabled until iter {args.precrop_iters}')
+        rows, cols = select_coords(H, W, args.N_rand, crop if cropped else None)
+        rows, cols = torch.as_tensor(rows, device=dev), torch.as_tensor(cols, device=dev)
+        rays_o, rays_d = rays_o[rows, cols], rays_d[rows, cols]
+        target = images[img_i].to(dev)[rows, cols]
+        t_data = time.time() - t0
+        loss, loss_rgb = trainer.step(rays_o, rays_d, target, lr, perturb=args.perturb, raw_noise_std=args.raw_noise_std)
+        loss_v, rgb_v = float(loss.item()), float(loss_rgb.item())
+        t_batch = time.time() - t0
+        if not math.isfinite(loss_v):
+            raise R2LError(f'the loss is {loss_v} at iteration {i} (LR {lr:.10f})')
+        psnr = mse2psnr(rgb_v)
+        hist_psnr = psnr if i == start + 1 else hist_psnr * 0.95 + psnr * 0.05
+        if i % args.i_print == 0:
+            log(f'[TRAIN] Iter {i} data_time {t_data:.4f} batch_time {t_batch:.4f} loss {loss_v:.6f} psnr {psnr:.4f} hist_psnr {hist_psnr:.4f} '
+                f'LR {lr:.10f}')
+        if i % args.i_testset == 0:                           # main.py:1442-1471
+            log(f'Iter {i} Testing...')
+            t_ = time.time()
+            tp, tp2 = eval_test_split(trainer, args, (H, W, focal), poses[i_test], images[i_test])
+            if tp2 > best_psnr:
+                best_psnr, best_psnr_step = tp2, i
+                best = save_train_checkpoint(os.path.join(weights_dir, 'ckpt_best.tar'), trainer, i, best_psnr, best_psnr_step)
+                log(f'Iter {i} Save the best checkpoint: "{best}".')
+            log(f'[TEST] Iter {i} TestPSNR {tp:.4f} TestPSNRv2 {tp2:.4f} BestPSNRv2 {best_psnr:.4f} (Iter {best_psnr_step}) '
+                f'TrainHistPSNR {hist_psnr:.4f} LR {lr:.8f} Time {time.time() - t_:.1f}s')
+        if i % args.i_weights == 0:
+            path = save_train_checkpoint(os.path.join(weights_dir, 'ckpt.tar'), trainer, i, best_psnr, best_psnr_step)
+            log(f'Iter {i} Save checkpoint: "{path}".')
+    if args.N_iters > start and args.N_iters % args.i_weights != 0:
+        path = save_train_checkpoint(os.path.join(weights_dir, 'ckpt.tar'), trainer, args.N_iters, best_psnr, best_psnr_step)
+        log(f'Iter {args.N_iters} Save checkpoint: "{path}".')
+    return path
+
+
+def main(argv=None):
+    from . import dist as D
+    from .frontend import parse_args
+    args = parse_args(argv)
+    if args.render_only:
+        raise SystemExit('train_teacher.py trains; render with main.py --model_name nerf --render_only --pretrained_ckpt X.tar')
+    check_supported(args)
+    torch.cuda.set_device(D.local_device(0))
+    train(args, log=lambda *a, **k: print(*a, **k, flush=True))
+    return 0

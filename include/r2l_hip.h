@@ -495,6 +495,16 @@ int r2l_train_adam(float* param_dev, const float* grad_dev, float* exp_avg_dev, 
  * t_rand over the strata of z_vals_dev [n_sample]; feeds r2l_sample_points with z_per_ray = 1 */
 int r2l_train_jitter_z(const float* z_vals_dev, const float* t_rand_dev, int n, int n_sample, float* z_out_dev, void* stream);
 
+/* ---- training of the NeRF teacher (csrc/nerf_train.hip; host mirror: efficient-nerf_amd/train_teacher.py) ----
+ * A teacher step is the launches above (layers, embedding, scans, loss, Adam) plus the backward pass of nerf_raw2outputs[_noise]:
+ * g_raw_dev [n,S,4] from g_rgb_map_dev [n,3], the only output the losses reach (main.py:728 detaches z_samples).  raw [n,S,4],
+ * z [n,S] per ray, rays_d [n,3], noise_dev [n,S] or NULL: the forward call's.  Division-free (a saturated sample, alpha = 1,
+ * leaves 1e-10 in the transmittance product; nothing divides by it), any S >= 1, no atomics: the same inputs give the same bits.
+ * The density gradient is exactly 0 where the relu is closed and on a last sample whose exp(-sigma 1e10) is 0.  g_raw_dev must
+ * not overlap raw_dev; both 16-byte aligned.  With n = 0 the buffers may be NULL. */
+int nerf_train_raw2outputs_backward(const float* raw_dev, const float* z_dev, const float* rays_d_dev, const float* noise_dev, int n,
+                                    int S, int white_bkgd, const float* g_rgb_map_dev, float* g_raw_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
