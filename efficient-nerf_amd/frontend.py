@@ -76,6 +76,8 @@ FLAGS = [
     ('--pseudo_ratio', dict(type=float, default=-1.)), ('--data_mode', dict(type=str, default='images', choices=['images', 'rays'])),
     ('--i_print', dict(type=int, default=100)), ('--i_weights', dict(type=int, default=10000)), ('--resume', dict(action=_BOOL)),
     ('--num_workers', dict(type=int, default=8)),
+    # ckpt_<i>.tar instead of ckpt.tar every --i_weights iterations (main.py:1510); the test split once from --pretrained_ckpt (main.py:1035)
+    ('--save_intermediate_models', dict(action=_BOOL)), ('--test_pretrained', dict(action=_BOOL)),
     # teacher training (train_teacher.py; names and defaults of option.py).  --no_batching, --precrop_iters and --precrop_frac above are
     # read by its loop
     ('--i_testset', dict(type=int, default=2000)), ('--i_video', dict(type=int, default=10000)),
@@ -312,6 +314,20 @@ def mse2psnr(mse):
     return -10. * math.log10(max(float(mse), 1e-30))
 
 
+def frame_errors(rgb, gt):
+    """(mean squared error, SSIM) of one [H, W, 3] frame against its ground truth, as device scalars (main.py:331-335)"""
+    from .metrics import ssim_hwc
+    return torch.mean((rgb - gt) ** 2), ssim_hwc(rgb, gt)
+
+
+def test_metrics(rgbs, gt, frame_mse, frame_ssim):
+    """The test report's three numbers (main.py:384-391): test_psnr from the mean error over all frames, test_psnr_v2 the mean
+    of the frames' PSNRs, test_ssim the mean of the frames' SSIMs.  rgbs, gt [N, H, W, 3] on one device; frame_mse / frame_ssim:
+    frame_errors of every frame."""
+    return {'test_psnr': mse2psnr(torch.mean((rgbs - gt) ** 2)), 'test_psnr_v2': float(np.mean([mse2psnr(m) for m in frame_mse])),
+            'test_ssim': float(np.mean([float(v) for v in frame_ssim]))}
+
+
 # ----------------------------------------------------------------------------------------
 # render_path
 # ----------------------------------------------------------------------------------------
@@ -541,7 +557,6 @@ def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=pr
     rank = tdist.get_rank() if tdist.is_initialized() else 0
     r0, r1 = D.row_shard(H, rank, world)
     n_local = (r1 - r0) * W
-    from .metrics import ssim_hwc
     n_frames = len(given_rays[0]) if given_rays is not None else len(render_poses)
     B = max(1, int(frames_per_batch or world))
     # the frame stack is allocated once and every batch is gathered straight into its slots: the collective's own buffer is
@@ -711,9 +726,9 @@ def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=pr
                 writer.put(os.path.join(savedir, f'{i0 + f:03d}.png'), host_stack[i0 + f], done)
         if gt_imgs is not None:
             for f in range(nb):
-                gt = gt_imgs[i0 + f].to(rgbs.device)
-                mse_dev.append(torch.mean((rgbs[i0 + f] - gt) ** 2))
-                ssim_dev.append(ssim_hwc(rgbs[i0 + f], gt))   # main.py:334-335
+                mse, ssim = frame_errors(rgbs[i0 + f], gt_imgs[i0 + f].to(rgbs.device))   # main.py:334-335
+                mse_dev.append(mse)
+                ssim_dev.append(ssim)
                 if writer is not None:  # main.py:340-341
                     writer.put(os.path.join(savedir, f'{i0 + f:03d}_gt.png'), gt_imgs[i0 + f].cpu().numpy())
         torch.cuda.synchronize()       # the reference's per-frame bracket (main.py:273-310), once per batch here
@@ -735,9 +750,7 @@ def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=pr
             stats['host_frames'] = host_stack          # complete: writer.close() has waited for every copy
     misc = {}
     if gt_imgs is not None:
-        misc['test_psnr'] = mse2psnr(torch.mean((rgbs - gt_imgs.to(rgbs.device)) ** 2))
-        misc['test_psnr_v2'] = float(np.mean([mse2psnr(m) for m in mse_dev]))
-        misc['test_ssim'] = float(np.mean([float(v) for v in ssim_dev]))
+        misc.update(test_metrics(rgbs, gt_imgs.to(rgbs.device), mse_dev, ssim_dev))
     return rgbs, misc
 
 

@@ -10,6 +10,7 @@ that are added in a fixed order, not with atomics).
 The network description is generic.v3_2_plan's: every shape the reference's constructor accepts.
 """
 import ctypes as C
+import json
 import math
 import os
 import time
@@ -384,6 +385,33 @@ class R2LTrainer(FlatAdam):
         """the last forward pass's output buffer [max_rays, 3]"""
         return self._acts[-1]
 
+    # ---- rendering from the live weights -----------------------------------------------------------------------------------
+    def render_rays(self, rays_o, rays_d, out=None):
+        """rgb [n, 3] of given rays from the weights as they stand in the flat buffer: PointSampler.sample_train without
+        perturbation -> embedding -> the training step's own forward launches, in chunks of at most max_rays.  The weights do not
+        leave the device and nothing is drawn.  The chunks run in the step's per-ray buffers (points, embedding, layer outputs),
+        all of which the next step's forward pass rewrites before its backward pass reads them; the gradients, Adam's moments,
+        the loss and the per-ray error are not touched."""
+        self._need_state()
+        n = rays_o.shape[0]
+        ro = rays_o.to(self.device, torch.float32).contiguous()
+        rd = rays_d.to(self.device, torch.float32).contiguous()
+        if tuple(ro.shape) != (n, 3) or tuple(rd.shape) != (n, 3):
+            raise R2LError(f'rays_o / rays_d are {tuple(ro.shape)} / {tuple(rd.shape)}, expected {(n, 3)}')
+        if out is None:
+            out = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            for s in range(0, n, self.max_rays):
+                m = min(self.max_rays, n - s)
+                out[s:s + m].copy_(self.forward(self.embed(ro[s:s + m], rd[s:s + m], perturb=0.), m))
+        return out
+
+    def render(self, c2w, H, W, focal, out=None):
+        """rgb [H * W, 3] of one pose (render_func, main.py:401-404) from the live weights"""
+        from .teacher import get_rays
+        ro, rd = get_rays(int(H), int(W), float(focal), torch.as_tensor(c2w)[:3, :4], device=self.device)
+        return self.render_rays(ro.view(-1, 3), rd.view(-1, 3), out=out)
+
 
 # ---------------------------------------------------------------------------------------------------------------------------
 # the loop of main.py:1136-1513
@@ -503,6 +531,51 @@ def trainer_from_args(args, max_rays):
                       max_rays=max_rays)
 
 
+def load_test_split(args, device=None):
+    """The test split the loop renders every --i_testset iterations (main.py:922-937, 1004-1012): ((poses, (H, W, focal), gt
+    [N, H, W, 3] on `device`), None), or (None, what is missing) when there is no test split to load.  A transforms_test.json
+    whose images are not there is an error: a half-copied scene must not train without the validation it asked for."""
+    from . import blender
+    if args.dataset_type != 'blender':
+        return None, f'--dataset_type {args.dataset_type} (test renders are built for --dataset_type blender)'
+    tf = os.path.join(args.datadir, 'transforms_test.json')
+    if not os.path.exists(tf):
+        return None, f'"{tf}"'
+    with open(tf) as fp:
+        frames = json.load(fp)['frames']
+    lost = [p for p in (os.path.join(args.datadir, f['file_path'] + '.png') for f in frames[::args.testskip or 1]) if not os.path.exists(p)]
+    if lost:
+        raise R2LError(f'"{tf}" names {len(lost)} image(s) that are not there, e.g. "{lost[0]}": complete the scene, or point --datadir elsewhere '
+                       f'to train without test renders')
+    imgs, poses, hwf, _ = blender.load_blender_data(args.datadir, args.half_res, args.testskip, splits=('test',))
+    gt = blender.composite(imgs, args.white_bkgd)
+    return (poses, (int(hwf[0]), int(hwf[1]), float(hwf[2])), gt if device is None else gt.to(device)), None
+
+
+def eval_test_split(trainer, test, savedir=None):
+    """render_path over the test split from the live weights (main.py:1442-1456): the frames [N, H, W, 3] on the device and
+    frontend.test_metrics' test_psnr, test_psnr_v2 and test_ssim; with savedir the frames as <k>.png.  test: load_test_split's,
+    its ground truth on the trainer's device."""
+    from .frontend import frame_errors, test_metrics, to8b, write_png
+    poses, (H, W, focal), gt = test
+    rgbs = torch.empty((len(poses), H, W, 3), dtype=torch.float32, device=trainer.device)
+    if gt.device != rgbs.device:
+        raise R2LError(f'the ground truth is on {gt.device}, the trainer on {rgbs.device}: load_test_split(args, device=trainer.device)')
+    mse_dev, ssim_dev = [], []
+    for k, pose in enumerate(poses):
+        trainer.render(pose, H, W, focal, out=rgbs[k].view(-1, 3))
+        mse, ssim = frame_errors(rgbs[k], gt[k])
+        mse_dev.append(mse)
+        ssim_dev.append(ssim)
+    misc = test_metrics(rgbs, gt, mse_dev, ssim_dev)
+    if savedir is not None:
+        os.makedirs(savedir, exist_ok=True)
+        host = rgbs.cpu().numpy()
+        for k in range(len(host)):
+            write_png(os.path.join(savedir, f'{k:03d}.png'), to8b(host[k]))
+    return rgbs, misc
+
+
 def train(args, log=print):
     """main.py without --render_only for --model_name R2L / nerf_v3.2, --data_mode rays."""
     from .create_data import BlenderDataset_v2
@@ -519,9 +592,16 @@ def train(args, log=print):
     batch_size = args.N_rand * split
     pool = HardRayPool(args.hard_ratio, args.hard_mul) if parse_hard_ratio(args.hard_ratio) else None
     n_hard_out = pool.counts(batch_size)[1] if pool else 0
+    if args.i_testset < 0:
+        raise SystemExit(f'--i_testset {args.i_testset}: a positive interval, or 0 for no test renders')
     trainer = trainer_from_args(args, batch_size + n_hard_out)
     dev = trainer.device
+    test, missing = load_test_split(args, device=dev)        # the ground truth goes to the device once
+    if args.test_pretrained and (test is None or not args.pretrained_ckpt):
+        raise SystemExit('--test_pretrained needs --pretrained_ckpt and a test split: ' +
+                         (f'{missing} is not there' if test is None else 'no --pretrained_ckpt was given'))
     start = 0
+    best_psnr, best_psnr_step = 0, 0
     if args.pretrained_ckpt:
         ckpt = load_checkpoint(args.pretrained_ckpt)
         trainer.load_state_dict(ckpt['network_fn_state_dict'])
@@ -529,13 +609,25 @@ def train(args, log=print):
         if args.resume:                                       # main.py:504-509
             start = int(ckpt['global_step'])
             trainer.load_optimizer_state_dict(ckpt['optimizer_state_dict'])
+            best_psnr, best_psnr_step = ckpt.get('best_psnr', 0), ckpt.get('best_psnr_step', 0)
             log('Resume optimizer successfully.')
     else:
         trainer.load_state_dict(init_state_dict(trainer.plan))
-    weights_dir = os.path.join(args.basedir, args.expname or 'train', 'weights')
+    expdir = os.path.join(args.basedir, args.expname or 'train')
+    weights_dir = os.path.join(expdir, 'weights')
     os.makedirs(weights_dir, exist_ok=True)
     log(f'Found {len(dataset)} shard(s) of {split} rays under "{datadir_kd}"; {args.N_rand} per step + {n_hard_out} hard rays; '
         f'{trainer.n_param} parameters in {len(trainer.plan)} layers, {trainer.activation_bytes() / 2 ** 30:.2f} GiB of saved activations')
+    if test is None:
+        log(f'No test renders during this run: {missing} is not there.')
+    else:
+        log(f'Test split: {len(test[0])} view(s) {test[1][0]} x {test[1][1]} from "{args.datadir}", ' +
+            (f'rendered every {args.i_testset} iterations' if args.i_testset else 'not rendered while training (--i_testset 0)'))
+    if args.test_pretrained:                                  # main.py:1035-1047
+        log('Testing pretrained...')
+        _, misc = eval_test_split(trainer, test)
+        log(f"Pretrained test: TestPSNR {misc['test_psnr']:.4f} TestPSNRv2 {misc['test_psnr_v2']:.4f}")
+    ckpt_name = lambda it: f'ckpt_{it}.tar' if args.save_intermediate_models else 'ckpt.tar'       # main.py:1510
     order = _infinite_order(len(dataset))
     hist_psnr = 0.
     t_data = t_batch = 0.
@@ -563,10 +655,23 @@ def train(args, log=print):
         if i % args.i_print == 0:
             log(f'[TRAIN] Iter {i} data_time {t_data:.4f} batch_time {t_batch:.4f} loss {loss_v:.6f} psnr {psnr:.4f} hist_psnr {hist_psnr:.4f} '
                 f'LR {lr:.10f}')
+        if test is not None and args.i_testset and i % args.i_testset == 0:      # main.py:1442-1471
+            testsavedir = os.path.join(expdir, f'testset_iter{i}')
+            log(f'Iter {i} Testing...')
+            t_ = time.time()
+            _, misc = eval_test_split(trainer, test, savedir=testsavedir)
+            t_test = time.time() - t_
+            if misc['test_psnr_v2'] > best_psnr:              # main.py:1458
+                best_psnr, best_psnr_step = misc['test_psnr_v2'], i
+                best = save_train_checkpoint(os.path.join(weights_dir, 'ckpt_best.tar'), trainer, i, best_psnr, best_psnr_step)
+                log(f'Iter {i} Save the best checkpoint: "{best}".')
+            log(f"[TEST] Iter {i} TestPSNR {misc['test_psnr']:.4f} TestPSNRv2 {misc['test_psnr_v2']:.4f} BestPSNRv2 {best_psnr:.4f} "
+                f"(Iter {best_psnr_step}) TestSSIM {misc['test_ssim']:.4f} TrainHistPSNR {hist_psnr:.4f} LR {lr:.8f} Time {t_test:.1f}s")
+            log(f'Saved rendered test images: "{testsavedir}"')
         if i % args.i_weights == 0:
-            path = save_train_checkpoint(os.path.join(weights_dir, 'ckpt.tar'), trainer, i)
+            path = save_train_checkpoint(os.path.join(weights_dir, ckpt_name(i)), trainer, i, best_psnr, best_psnr_step)
             log(f'Iter {i} Save checkpoint: "{path}".')
     if args.N_iters > start and args.N_iters % args.i_weights != 0:
-        path = save_train_checkpoint(os.path.join(weights_dir, 'ckpt.tar'), trainer, args.N_iters)
+        path = save_train_checkpoint(os.path.join(weights_dir, ckpt_name(args.N_iters)), trainer, args.N_iters, best_psnr, best_psnr_step)
         log(f'Iter {args.N_iters} Save checkpoint: "{path}".')
     return path

@@ -495,6 +495,17 @@ int r2l_train_adam(float* param_dev, const float* grad_dev, float* exp_avg_dev, 
  * t_rand over the strata of z_vals_dev [n_sample]; feeds r2l_sample_points with z_per_ray = 1 */
 int r2l_train_jitter_z(const float* z_vals_dev, const float* t_rand_dev, int n, int n_sample, float* z_out_dev, void* stream);
 
+/* ---- real images to ray rows (csrc/r2l_convert.hip; host mirror: efficient-nerf_amd/convert_data.py) ----
+ * utils/convert_original_data_to_rays_blender.py:142-223 as one gather: out_dev [rows, 9] = (rays_o, rays_d, rgb) of the pixels
+ * order_dev [rows] names (int64, device): order[k] = image * H * W + row * W + column on the output grid, H x W = H0 x W0, or
+ * H0/2 x W0/2 with half_res.  images_dev: uint8 [n_img, H0, W0, channels], channels 3 or 4; poses_dev: float32 [n_img, 3, 4];
+ * focal: of the output grid (already halved with half_res).  Colours are bytes / 255, under half_res the mean of the 2 x 2 block
+ * (cv2.INTER_AREA for a factor of two); four channels are composited on white (rgb * a + (1 - a)), three are kept as they are.
+ * Rays are get_rays' (:69-86).  One thread per row, plain stores, no atomics: the same inputs give the same bits.  An index outside
+ * [0, n_img * H * W) reads nothing and leaves a row of NaN. */
+int r2l_rays_from_images(const unsigned char* images_dev, int n_img, int H0, int W0, int channels, const float* poses_dev, double focal,
+                         int half_res, const long long* order_dev, long long rows, float* out_dev, void* stream);
+
 /* ---- training of the NeRF teacher (csrc/nerf_train.hip; host mirror: efficient-nerf_amd/train_teacher.py) ----
  * A teacher step is the launches above (layers, embedding, scans, loss, Adam) plus the backward pass of nerf_raw2outputs[_noise]:
  * g_raw_dev [n,S,4] from g_rgb_map_dev [n,3], the only output the losses reach (main.py:728 detaches z_samples).  raw [n,S,4],
