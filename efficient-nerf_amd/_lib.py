@@ -125,6 +125,8 @@ SIGNATURES = {
     'r2l_train_jitter_z': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp]),
     # real images to ray rows (csrc/r2l_convert.hip)
     'r2l_rays_from_images': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_double, C.c_int, _vp, C.c_longlong, _vp, _vp]),
+    # rays for online distillation (csrc/r2l_online.hip)
+    'r2l_rand_rays': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_longlong, C.c_longlong, _vp, _vp, _vp, _vp]),
     # teacher training (csrc/nerf_train.hip)
     'nerf_train_raw2outputs_backward': (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
 }

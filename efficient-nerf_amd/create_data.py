@@ -551,12 +551,35 @@ class BlenderDataset_v2:
         return tuple(rows[..., s] for s in self.cols)
 
 
+def build_teacher_engine(args, ckpt, hwf, use_rand_focal=True, log=None, watched='per save group'):
+    """The teacher that renders random poses over the hemisphere at focal x [1, 2) -- create_data rand's shards and the online source
+    of train.py: args = the teacher's own flags (frontend.parse_args), ckpt = its checkpoint, hwf = (H, W, focal).  A teacher the
+    fused kernels are not built for renders on the generic fp32 layer path; otherwise a NeRFEngine, under `--precision auto` in the
+    mode choose_precision_for_rand measures on this checkpoint (watched: how often the caller spot-checks that choice, for the log)."""
+    from . import frontend as fe
+    from . import NeRFEngine, PRECISIONS
+    H, W, focal = hwf
+    if fe.teacher_needs_generic(args):     # a teacher the fused kernels are not built for: the generic fp32 layer path renders it
+        args.model_name, args.dataset_type = 'nerf', 'blender'
+        _, eng = fe.build_engine(args, (H, W, focal), ckpt, log=log)
+        return eng
+    auto = args.precision == 'auto'
+    eng = NeRFEngine(H, W, focal, 2., 6., N_samples=args.N_samples, N_importance=args.N_importance,
+                     white_bkgd=args.white_bkgd, precision=PRECISIONS['fp16x3' if auto else args.precision])
+    eng.load_state_dicts(ckpt['network_fn_state_dict'], ckpt['network_fine_state_dict'])
+    if auto:       # measured on this checkpoint, on rays of poses spanning the distribution the job samples (every rank the same)
+        name = choose_precision_for_rand(eng, H, W, focal, use_rand_focal)
+        if log:
+            log(f'[precision] auto: largest rgb / acc difference from fp16x3 on 4,096 rays of each of {len(RAND_PROBES)} probe poses '
+                f'(top-down ... horizontal, focal x 1 ... x 2): {eng.auto_diffs} -> {name}; watched {watched}')
+    return eng
+
+
 def main(argv=None):
     """`python create_data.py --create_data rand --config configs/lego.txt --teacher_ckpt X.tar
     --n_pose_kd N --datadir_kd old:new` (README.md:79 of the reference)."""
     import argparse
     from . import frontend as fe
-    from . import NeRFEngine, PRECISIONS
     ap = argparse.ArgumentParser(add_help=False)
     ap.add_argument('--create_data', type=str, default='spiral_evenly_spaced')
     ap.add_argument('--teacher_ckpt', type=str, default='')
@@ -576,19 +599,7 @@ def main(argv=None):
     torch.cuda.set_device(D.local_device(local_rank))
     ckpt = fe.load_checkpoint(own.teacher_ckpt)
     _, (H, W, focal) = fe.load_test_poses(args)
-    if fe.teacher_needs_generic(args):     # a teacher the fused kernels are not built for: the generic fp32 layer path renders it
-        args.model_name, args.dataset_type = 'nerf', 'blender'
-        _, eng = fe.build_engine(args, (H, W, focal), ckpt, log=print if rank == 0 else None)
-    else:
-        auto = args.precision == 'auto'
-        eng = NeRFEngine(H, W, focal, 2., 6., N_samples=args.N_samples, N_importance=args.N_importance,
-                         white_bkgd=args.white_bkgd, precision=PRECISIONS['fp16x3' if auto else args.precision])
-        eng.load_state_dicts(ckpt['network_fn_state_dict'], ckpt['network_fine_state_dict'])
-        if auto:       # measured on this checkpoint, on rays of poses spanning the distribution the job samples (every rank the same)
-            name = choose_precision_for_rand(eng, H, W, focal, not own.no_rand_focal)
-            if rank == 0:
-                print(f'[precision] auto: largest rgb / acc difference from fp16x3 on 4,096 rays of each of {len(RAND_PROBES)} probe poses '
-                      f'(top-down ... horizontal, focal x 1 ... x 2): {eng.auto_diffs} -> {name}; watched per save group')
+    eng = build_teacher_engine(args, ckpt, (H, W, focal), not own.no_rand_focal, log=print if rank == 0 else None)
     tm = {}
     n = create_rand(eng, H, W, focal, own.n_pose_kd, own.datadir_kd.split(':')[1], not own.no_rand_focal,
                     i_save=own.create_data_chunk, split_size=own.split_size, rm_existing_data=own.rm_existing_data,

@@ -76,6 +76,14 @@ FLAGS = [
     ('--pseudo_ratio', dict(type=float, default=-1.)), ('--data_mode', dict(type=str, default='images', choices=['images', 'rays'])),
     ('--i_print', dict(type=int, default=100)), ('--i_weights', dict(type=int, default=10000)), ('--resume', dict(action=_BOOL)),
     ('--num_workers', dict(type=int, default=8)),
+    # online distillation (online.py): the teacher renders every step's rays on the device instead of --datadir_kd's shards.  --teacher_config:
+    # the teacher's own flags (default: lego.txt beside --config); --kd_online_poses random poses are mixed into a step (100: one save group of
+    # create_data rand), drawn from (--kd_online_seed, step); the teacher's mode is spot-checked every --kd_online_watch steps (0: never); a
+    # step carries --N_rand x --kd_online_split rays
+    ('--kd_online', dict(action=_BOOL)), ('--teacher_ckpt', dict(type=str, default='')), ('--teacher_config', dict(type=str, default='')),
+    ('--kd_online_poses', dict(type=int, default=100)), ('--kd_online_seed', dict(type=int, default=0)),
+    ('--kd_online_watch', dict(type=int, default=100)), ('--kd_online_split', dict(type=int, default=4096)),
+    ('--no_rand_focal', dict(action=_BOOL)),
     # ckpt_<i>.tar instead of ckpt.tar every --i_weights iterations (main.py:1510); the test split once from --pretrained_ckpt (main.py:1035)
     ('--save_intermediate_models', dict(action=_BOOL)), ('--test_pretrained', dict(action=_BOOL)),
     # teacher training (train_teacher.py; names and defaults of option.py).  --no_batching, --precrop_iters and --precrop_frac above are
@@ -761,7 +769,10 @@ def main(argv=None):
         if args.model_name not in ('R2L', 'nerf_v3.2'):
             raise SystemExit(f'--model_name {args.model_name} without --render_only: teacher training is not built (the student trains: '
                              f'--model_name R2L --data_mode rays --datadir_kd DIR) into main.py: train_teacher.py takes the same flags')
-        if args.data_mode != 'rays' or not args.datadir_kd:
+        if args.kd_online:
+            from .online import check_online_args
+            check_online_args(args)
+        elif args.data_mode != 'rays' or not args.datadir_kd:
             raise SystemExit('without --render_only main.py trains the student, which is built for ray shards: pass --data_mode rays '
                              '--datadir_kd DIR (or --render_only --pretrained_ckpt X.tar to render)')
         from . import train as T

@@ -1,0 +1,136 @@
+"""Online distillation: the teacher renders every step's rays on the card the student trains on.
+
+The reference's pipeline meets on the disk: `create_data rand` writes the teacher's renders of 10,000 random poses as ray shards and
+`main.py` reads 20 of them per step, because its teacher takes seconds per frame.  Here the teacher (NeRFEngine) and the student's
+trainer (train.R2LTrainer) are launches of one library on one device, so a step can ask for fresh rays instead:
+
+    OnlineTeacherSource.batch(step, n)
+        host     n_pose random poses and focals, the draws of create_data rand in its order (per pose theta, phi, then the focal
+                 scale: RandStream.rand_pose / rand_focal_scale) from np.random.RandomState((seed, step))
+        device   one r2l_rand_rays launch (csrc/r2l_online.hip): ray k = a Philox-drawn pixel of pose k % n_pose, get_rays' ray
+        device   engine.render_rays(rays_o, rays_d)['rgb_map']: the target
+
+A batch is a function of (seed, step) alone -- nothing of the source has to be saved in a checkpoint, and a resumed run sees the
+batches the uninterrupted run saw.  (The teacher's mode is the one exception: `--precision auto` measures it again at start-up, and a
+watch that stepped down in the first run has to step down again; the modes differ by less than the watch's limits.)
+
+The watch of create_rand and render_path carries over: every watch_every-th step the batch is spot-checked against fp16x3 before it
+is handed on (NeRFEngine.spot_check); a miss moves the engine one rung down its ladder and the batch is rendered again."""
+import os
+
+import numpy as np
+import torch
+
+from ._lib import R2LError, check, current_stream, dptr, lib
+
+
+class OnlineTeacherSource:
+    """engine: what renders the targets (render_rays(rays_o, rays_d) -> {'rgb_map': [n, 3]}; spot_check / step_down / set_skip_rgb0
+    where it has them: NeRFEngine, or generic.GenericNeRF for teachers outside the fused kernels).  (H, W, focal): the camera the
+    random poses look through; with use_rand_focal every pose draws its own focal in [focal, 2 focal).  watch_every: 0 = never.
+    rays_fn(poses [n_pose, 3, 4], focals [n_pose] float32, step, n) -> (rays_o, rays_d): replaces the r2l_rand_rays launch."""
+
+    def __init__(self, engine, H, W, focal, n_pose=100, seed=0, use_rand_focal=True, watch_every=100, log=print, rays_fn=None):
+        self.engine, self.H, self.W, self.focal = engine, int(H), int(W), float(focal)
+        self.n_pose, self.seed, self.use_rand_focal = int(n_pose), int(seed), bool(use_rand_focal)
+        self.watch_every, self.log = int(watch_every), log or (lambda *a, **k: None)
+        if self.n_pose < 1 or not 1 <= self.H * self.W < 2 ** 31 or not self.focal > 0:
+            raise R2LError(f'n_pose={n_pose} H={H} W={W} focal={focal}')
+        if not 0 <= self.seed < 2 ** 32 or self.watch_every < 0:
+            raise R2LError(f'seed={seed} (0 .. 2^32 - 1: one word of the RandomState seed) watch_every={watch_every}')
+        self.device = torch.device(getattr(engine, 'device', 'cpu'))
+        self._rays_fn = rays_fn or self._launch_rays
+        self.checks, self.fallbacks = 0, []
+        if hasattr(engine, 'set_skip_rgb0'):
+            engine.set_skip_rgb0(True)        # only rgb_map is taken (as create_rand does): the coarse pass runs without its view branch
+
+    def draws(self, step):
+        """(poses [n_pose, 3, 4] float32, focals [n_pose] float64) of a step, on the host"""
+        from .create_data import RandStream
+        if not 0 <= int(step) < 2 ** 32:
+            raise R2LError(f'step={step}')
+        stream = RandStream(seed=(self.seed, int(step)), n_loader_poses=0)
+        poses, focals = [], np.empty(self.n_pose, dtype=np.float64)
+        for p in range(self.n_pose):
+            poses.append(stream.rand_pose()[:3, :4])
+            focals[p] = self.focal * stream.rand_focal_scale() if self.use_rand_focal else self.focal
+        return torch.stack(poses, 0).contiguous(), focals
+
+    def _launch_rays(self, poses, focals, step, n):
+        dev = self.device
+        po, fo = poses.to(dev), focals.to(dev)
+        ro = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        rd = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            check(lib().r2l_rand_rays(dptr(po), dptr(fo), self.n_pose, self.H, self.W, self.seed, int(step), n, dptr(ro), dptr(rd), None,
+                                      current_stream()))
+        return ro, rd
+
+    def batch(self, step, n):
+        """(rays_o, rays_d, target), each [n, 3] float32 on the engine's device"""
+        step, n = int(step), int(n)
+        poses, focals = self.draws(step)
+        ro, rd = self._rays_fn(poses, torch.from_numpy(focals).to(torch.float32), step, n)       # get_rays rounds the focal the same way
+        eng = self.engine
+        out = eng.render_rays(ro, rd)
+        if self.watch_every and step % self.watch_every == 0 and hasattr(eng, 'spot_check'):
+            for _ in range(len(getattr(eng, 'LADDER', (0,)))):
+                ok, d = eng.spot_check(ro, rd, out)
+                self.checks += 1
+                if ok:
+                    break
+                was = getattr(eng, 'precision_name', '?')
+                now = eng.step_down()
+                self.fallbacks.append({'step': step, 'from': was, 'to': now, 'diffs': d})
+                out = eng.render_rays(ro, rd)
+                self.log(f'[precision] step {step}: {was} is {d} from fp16x3 on {getattr(eng, "WATCH_RAYS", "a sample")} of the batch\'s rays -> {now}; '
+                         f'batch rendered again')
+        return ro, rd, out['rgb_map']
+
+
+def check_online_args(args):
+    """the command lines --kd_online refuses, one line each"""
+    if args.datadir_kd:
+        raise SystemExit(f'--kd_online renders every step\'s rays with the teacher; --datadir_kd {args.datadir_kd} names ray shards: pass one of the two')
+    if not args.teacher_ckpt:
+        raise SystemExit('--kd_online needs --teacher_ckpt X.tar (the NeRF teacher that renders the rays)')
+    if args.dataset_type != 'blender':
+        raise SystemExit(f'--kd_online with --dataset_type {args.dataset_type}: the random poses are Blender\'s hemisphere (--dataset_type blender)')
+    if args.kd_online_poses < 1 or args.kd_online_split < 1 or args.kd_online_watch < 0 or not 0 <= args.kd_online_seed < 2 ** 32:
+        raise SystemExit(f'--kd_online_poses {args.kd_online_poses} --kd_online_split {args.kd_online_split} --kd_online_watch '
+                         f'{args.kd_online_watch} --kd_online_seed {args.kd_online_seed}: at least one pose and one ray, a watch interval >= 0, a seed '
+                         f'in 0 .. 2^32 - 1')
+
+
+def teacher_args(args):
+    """The teacher's own flags (use_viewdirs, N_samples, N_importance, white_bkgd, half_res, the network's shape): --teacher_config, by
+    default configs' lego.txt beside the student's --config.  The scene, the image size and --precision are the command line's."""
+    from . import frontend as fe
+    path = args.teacher_config or (os.path.join(os.path.dirname(os.path.abspath(args.config)), 'lego.txt') if args.config else '')
+    if not path or not os.path.exists(path):
+        raise SystemExit(f'--kd_online reads the teacher\'s flags from --teacher_config FILE (default: lego.txt beside --config): '
+                         f'"{path}" is not there')
+    t = fe.parse_args(['--config', path])
+    t.datadir, t.H, t.W, t.synthetic_poses, t.precision = args.datadir, args.H, args.W, args.synthetic_poses, args.precision
+    return t
+
+
+def source_from_args(args, log=print):
+    """(OnlineTeacherSource, the start-up line's description of it) for train.train under --kd_online, which has refused what
+    check_online_args refuses"""
+    from . import frontend as fe
+    from .create_data import build_teacher_engine
+    t = teacher_args(args)
+    ckpt = fe.load_checkpoint(args.teacher_ckpt)
+    _, (H, W, focal) = fe.load_test_poses(t)
+    rand_focal = not args.no_rand_focal
+    eng = build_teacher_engine(t, ckpt, (H, W, focal), rand_focal, log=log,
+                               watched=f'every {args.kd_online_watch} steps' if args.kd_online_watch else 'never (--kd_online_watch 0)')
+    src = OnlineTeacherSource(eng, H, W, focal, n_pose=args.kd_online_poses, seed=args.kd_online_seed, use_rand_focal=rand_focal,
+                              watch_every=args.kd_online_watch, log=log)
+    mode = getattr(eng, 'precision_name', 'fp32')
+    what = (f'teacher "{args.teacher_ckpt}" in {mode}' + (' (chosen by --precision auto)' if args.precision == 'auto' and mode != 'fp32' else '') +
+            f', {src.n_pose} random poses of {H} x {W} per step at focal ' +
+            (f'{focal:.2f} .. {2 * focal:.2f}' if rand_focal else f'{focal:.2f}') +
+            f', seed {src.seed}, ' + (f'watched every {src.watch_every} steps' if src.watch_every else 'not watched'))
+    return src, what

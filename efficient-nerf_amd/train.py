@@ -577,18 +577,36 @@ def eval_test_split(trainer, test, savedir=None):
 
 
 def train(args, log=print):
-    """main.py without --render_only for --model_name R2L / nerf_v3.2, --data_mode rays."""
+    """_train, and whatever ends it, the teacher engine of --kd_online is closed"""
+    engines = []
+    try:
+        return _train(args, log, engines)
+    finally:
+        for eng in engines:
+            if hasattr(eng, 'close'):
+                eng.close()
+
+
+def _train(args, log, engines):
+    """main.py without --render_only for --model_name R2L / nerf_v3.2, --data_mode rays; with --kd_online the rays of every step are
+    rendered by the teacher on the device (online.py) instead of read from shards, and everything behind them is the same code."""
     from .create_data import BlenderDataset_v2
     from .frontend import load_checkpoint, mse2psnr
-    if args.data_mode != 'rays':
-        raise R2LError(f'--data_mode {args.data_mode}: training is built for --data_mode rays (the shards create_data.py writes)')
-    if not args.datadir_kd:
-        raise R2LError('training needs --datadir_kd (a directory of ray shards)')
-    datadir_kd = args.datadir_kd.split(':')[1] if ':' in args.datadir_kd else args.datadir_kd        # main.py:1052-1053
-    dataset = BlenderDataset_v2(datadir_kd, dim_dir=3, dim_rgb=3, pseudo_ratio=args.pseudo_ratio)
-    if len(dataset) == 0:
-        raise R2LError(f'no .npy shards under {datadir_kd}')
-    split = int(dataset[0][0].shape[0])
+    online = bool(getattr(args, 'kd_online', False))
+    if online:                 # every step's rays from the teacher (online.py) instead of shards
+        from .online import check_online_args, source_from_args
+        check_online_args(args)
+        dataset, split = None, int(args.kd_online_split)
+    else:
+        if args.data_mode != 'rays':
+            raise R2LError(f'--data_mode {args.data_mode}: training is built for --data_mode rays (the shards create_data.py writes)')
+        if not args.datadir_kd:
+            raise R2LError('training needs --datadir_kd (a directory of ray shards)')
+        datadir_kd = args.datadir_kd.split(':')[1] if ':' in args.datadir_kd else args.datadir_kd        # main.py:1052-1053
+        dataset = BlenderDataset_v2(datadir_kd, dim_dir=3, dim_rgb=3, pseudo_ratio=args.pseudo_ratio)
+        if len(dataset) == 0:
+            raise R2LError(f'no .npy shards under {datadir_kd}')
+        split = int(dataset[0][0].shape[0])
     batch_size = args.N_rand * split
     pool = HardRayPool(args.hard_ratio, args.hard_mul) if parse_hard_ratio(args.hard_ratio) else None
     n_hard_out = pool.counts(batch_size)[1] if pool else 0
@@ -596,6 +614,9 @@ def train(args, log=print):
         raise SystemExit(f'--i_testset {args.i_testset}: a positive interval, or 0 for no test renders')
     trainer = trainer_from_args(args, batch_size + n_hard_out)
     dev = trainer.device
+    if online:
+        source, source_desc = source_from_args(args, log=log)
+        engines.append(source.engine)
     test, missing = load_test_split(args, device=dev)        # the ground truth goes to the device once
     if args.test_pretrained and (test is None or not args.pretrained_ckpt):
         raise SystemExit('--test_pretrained needs --pretrained_ckpt and a test split: ' +
@@ -616,7 +637,8 @@ def train(args, log=print):
     expdir = os.path.join(args.basedir, args.expname or 'train')
     weights_dir = os.path.join(expdir, 'weights')
     os.makedirs(weights_dir, exist_ok=True)
-    log(f'Found {len(dataset)} shard(s) of {split} rays under "{datadir_kd}"; {args.N_rand} per step + {n_hard_out} hard rays; '
+    log((f'Online distillation: {source_desc}; {batch_size} rays per step + {n_hard_out} hard rays; ' if online else
+         f'Found {len(dataset)} shard(s) of {split} rays under "{datadir_kd}"; {args.N_rand} per step + {n_hard_out} hard rays; ') +
         f'{trainer.n_param} parameters in {len(trainer.plan)} layers, {trainer.activation_bytes() / 2 ** 30:.2f} GiB of saved activations')
     if test is None:
         log(f'No test renders during this run: {missing} is not there.')
@@ -628,7 +650,7 @@ def train(args, log=print):
         _, misc = eval_test_split(trainer, test)
         log(f"Pretrained test: TestPSNR {misc['test_psnr']:.4f} TestPSNRv2 {misc['test_psnr_v2']:.4f}")
     ckpt_name = lambda it: f'ckpt_{it}.tar' if args.save_intermediate_models else 'ckpt.tar'       # main.py:1510
-    order = _infinite_order(len(dataset))
+    order = None if online else _infinite_order(len(dataset))
     hist_psnr = 0.
     t_data = t_batch = 0.
     path = None
@@ -636,12 +658,17 @@ def train(args, log=print):
     for i in range(start + 1, args.N_iters + 1):
         t0 = time.time()
         lr = learning_rate(i, args.lrate, args.lrate_decay, args.warmup_lr)
-        items = [dataset[int(next(order))] for _ in range(args.N_rand)]
-        rays_o, rays_d, target = (torch.cat([it[k] for it in items], 0).to(dev) for k in range(3))
+        if online:
+            rays_o, rays_d, target = source.batch(i, batch_size)
+        else:
+            items = [dataset[int(next(order))] for _ in range(args.N_rand)]
+            rays_o, rays_d, target = (torch.cat([it[k] for it in items], 0).to(dev) for k in range(3))
         if pool is not None:
             picked = pool.draw(batch_size)
             if picked is not None:
                 rays_o, rays_d, target = (torch.cat([a, picked[:, 3 * k:3 * k + 3]], 0) for k, a in enumerate((rays_o, rays_d, target)))
+        if online:
+            torch.cuda.synchronize(dev)       # data_time contains the teacher's render
         t_data = time.time() - t0
         loss, err = trainer.step(rays_o, rays_d, target, lr, perturb=args.perturb)
         if pool is not None:

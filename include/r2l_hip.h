@@ -506,6 +506,16 @@ int r2l_train_jitter_z(const float* z_vals_dev, const float* t_rand_dev, int n, 
 int r2l_rays_from_images(const unsigned char* images_dev, int n_img, int H0, int W0, int channels, const float* poses_dev, double focal,
                          int half_res, const long long* order_dev, long long rows, float* out_dev, void* stream);
 
+/* ---- rays for online distillation (csrc/r2l_online.hip; host mirror: efficient-nerf_amd/online.py) ----
+ * n random rays of n_pose cameras: ray k belongs to pose k % n_pose and to the pixel mulhi32(x, H * W) of its H x W grid, x = word 0
+ * of Philox4x32-10 with counter (k_lo, k_hi, step_lo, step_hi) and key (seed_lo, seed_hi); the relative bias of a pixel's share is
+ * at most H * W / 2^32, and 1 <= H * W < 2^31.  poses_dev: float32 [n_pose, 3, 4]; focal_dev: float32 [n_pose], each pose's own focal.
+ * rays_o_dev / rays_d_dev [n, 3] are get_rays' (utils/run_nerf_raybased_helpers.py:231-257) for that pixel, bit for bit what
+ * nerf_get_rays writes for it; pixel_dev [n] (int64, may be NULL) receives row * W + column.  One thread per ray, plain stores, no
+ * atomics: the output is a function of the arguments alone.  n = 0 is a no-op. */
+int r2l_rand_rays(const float* poses_dev, const float* focal_dev, int n_pose, int H, int W, unsigned long long seed, long long step,
+                  long long n, float* rays_o_dev, float* rays_d_dev, long long* pixel_dev, void* stream);
+
 /* ---- training of the NeRF teacher (csrc/nerf_train.hip; host mirror: efficient-nerf_amd/train_teacher.py) ----
  * A teacher step is the launches above (layers, embedding, scans, loss, Adam) plus the backward pass of nerf_raw2outputs[_noise]:
  * g_raw_dev [n,S,4] from g_rgb_map_dev [n,3], the only output the losses reach (main.py:728 detaches z_samples).  raw [n,S,4],
