@@ -88,6 +88,7 @@ SIGNATURES = {
     'nerf_ndc_rays': (C.c_int, [C.c_int, C.c_int, C.c_double, C.c_float, _vp, _vp, C.c_int, _vp, _vp, _vp]),
     'nerf_debug_pack_chain_host': (C.c_longlong, [C.POINTER(_vp), C.c_int, C.c_int, _vp, C.c_longlong, C.POINTER(C.c_longlong)]),
     'nerf_run_network': (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
+    'nerf_run_network_dirs': (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp]),
     'nerf_sample_pdf_u': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, C.c_int, _vp, _vp]),
     'nerf_render': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp]),
     'nerf_render_rays': (C.c_int, [_vp, _vp, _vp, C.c_int, _vp, _vp, _vp, _vp, _vp]),

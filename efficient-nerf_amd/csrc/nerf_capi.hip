@@ -913,14 +913,19 @@ long long nerf_debug_pack_chain_host(const float* const* tensors, int n_tensors,
     return (long long)img.size();
 }
 
-int nerf_run_network(nerf_ctx* c, int which, const float* rays_o_dev, const float* rays_d_dev, const float* z_dev,
-                     int z_stride, int S, int n, float* raw_dev, void* stream) {
+int nerf_run_network_dirs(nerf_ctx* c, int which, const float* rays_o_dev, const float* rays_d_dev, const float* viewdirs_dev,
+                          const float* z_dev, int z_stride, int S, int n, float* raw_dev, void* stream) {
     if (!c || !rays_o_dev || !rays_d_dev || !z_dev || !raw_dev) return r2l_set_error(R2L_EINVAL, "NULL argument");
     if (which != 0 && which != 1) return r2l_set_error(R2L_EINVAL, "which=%d", which);
     if (!c->net[which].loaded) return r2l_set_error(R2L_ESTATE, "network %d not loaded", which);
     if (S < 1 || n < 0 || (z_stride != 0 && z_stride < S)) return r2l_set_error(R2L_EINVAL, "bad S/n/z_stride");
     if (n == 0) return R2L_OK;
-    return run_mlp(c, which, rays_o_dev, rays_d_dev, z_dev, z_stride, S, n, raw_dev, (hipStream_t)stream);
+    return run_mlp(c, which, rays_o_dev, rays_d_dev, z_dev, z_stride, S, n, raw_dev, (hipStream_t)stream, viewdirs_dev);
+}
+
+int nerf_run_network(nerf_ctx* c, int which, const float* rays_o_dev, const float* rays_d_dev, const float* z_dev,
+                     int z_stride, int S, int n, float* raw_dev, void* stream) {
+    return nerf_run_network_dirs(c, which, rays_o_dev, rays_d_dev, nullptr, z_dev, z_stride, S, n, raw_dev, stream);
 }
 
 int nerf_raw2outputs_noise(const float* raw, const float* z, const float* rays_d, const float* noise, int n, int S,

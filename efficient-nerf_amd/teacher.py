@@ -526,12 +526,17 @@ class NeRFEngine:
     def _x3_pair(self, ro, rd, ref):
         """fp16x3_asm (the current mode) against `ref` = what fp16x3 rendered for these rays with extras: ({output: largest difference},
         ok) -- stage by stage, see AUTO_MAX_DIFF_X3ASM: the coarse maps of a full render, then the FINE network and its compositing at
-        the reference's own sample positions (run_network + raw2outputs on ref['z_vals'])"""
+        the reference's own sample positions (run_network + raw2outputs on ref['z_vals']).  On an NDC engine those positions lie on the
+        PROJECTED rays and the networks see the world rays' directions, as in the render itself (render_rays_dev; main.py:148-162)"""
         lim = self._limits(self.AUTO_MAX_DIFF_X3ASM)
         lim['rgb0'] = lim['acc0'] = self.AUTO_MAX_DIFF_X3ASM
         got = self.render_rays(ro, rd, extras=True)
         d = {k: float((got[k] - ref[k]).abs().max()) for k in ('rgb0', 'acc0')}
-        raw = self.run_network(1, ro, rd, ref['z_vals'])
+        vd = None
+        if self.ndc:
+            vd = rd / torch.norm(rd, dim=-1, keepdim=True)
+            ro, rd = ndc_rays(self.H, self.W, self.focal, 1., ro, rd)
+        raw = self.run_network(1, ro, rd, ref['z_vals'], viewdirs=vd)
         rgb, _, acc, _, depth = raw2outputs(raw, ref['z_vals'], rd, white_bkgd=self.white_bkgd)
         tie = self._far_ties(raw, ref['raw']) if 'raw' in ref else None
         d.update(self._map_diffs({'rgb_map': rgb, 'acc_map': acc, 'depth_map': depth}, ref, tie))
@@ -689,18 +694,24 @@ class NeRFEngine:
                 ret.update(self._extras(n))
         return ret
 
-    def run_network(self, which, rays_o, rays_d, z_vals):
+    def run_network(self, which, rays_o, rays_d, z_vals, viewdirs=None):
         """network_query_fn(pts, viewdirs, network) of main.py:447-453 with
-        pts = rays_o + rays_d * z_vals: raw [n,S,4]."""
+        pts = rays_o + rays_d * z_vals: raw [n,S,4].  viewdirs ([n,3], one direction per ray): embedded as given instead of
+        rays_d / |rays_d| -- a forward-facing render's networks see the world rays' directions at points of the projected rays
+        (main.py:148-162; nerf_run_network_dirs)."""
         rays_o, rays_d = _f32(rays_o, self.device), _f32(rays_d, self.device)
         n = rays_o.shape[0]
+        if viewdirs is not None:
+            viewdirs = _f32(viewdirs, self.device)
+            if tuple(viewdirs.shape) != (n, 3):
+                raise R2LError(f'viewdirs must be [{n}, 3]; got {tuple(viewdirs.shape)}')
         z = _f32(z_vals, self.device)
         shared = z.dim() == 1
         S = z.shape[-1]
         raw = torch.empty((n, S, 4), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
-            check(lib().nerf_run_network(self._ctx, int(which), dptr(rays_o), dptr(rays_d), dptr(z), 0 if shared else S,
-                                         S, n, dptr(raw), current_stream()))
+            check(lib().nerf_run_network_dirs(self._ctx, int(which), dptr(rays_o), dptr(rays_d), dptr(viewdirs), dptr(z),
+                                              0 if shared else S, S, n, dptr(raw), current_stream()))
         return raw
 
 

@@ -387,6 +387,12 @@ int nerf_get_rays(int H, int W, double focal, const float* c2w_host, int row_beg
  * row (z_stride = 0), both embedders, network `which` -> raw_dev [n,S,4] = (rgb, sigma). */
 int nerf_run_network(nerf_ctx* ctx, int which, const float* rays_o_dev, const float* rays_d_dev,
                      const float* z_dev, int z_stride, int S, int n, float* raw_dev, void* stream);
+/* the same with GIVEN view directions viewdirs_dev [n,3], one per ray, embedded as they are (main.py:76-77) instead of
+ * rays_d / |rays_d|: what a forward-facing render hands its networks (view directions of the world rays, points along the
+ * projected rays: main.py:148-162).  viewdirs_dev = NULL is exactly nerf_run_network. */
+int nerf_run_network_dirs(nerf_ctx* ctx, int which, const float* rays_o_dev, const float* rays_d_dev,
+                          const float* viewdirs_dev, const float* z_dev, int z_stride, int S, int n,
+                          float* raw_dev, void* stream);
 
 /* Host-only: the R2L_PREC_FP16_FP8 image of one teacher network that nerf_load_weights uploads for
  * nerf_chain_kernel (the layer chain's weight stream followed by the 16 KiB bias / scale table; layout:
