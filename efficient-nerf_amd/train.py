@@ -9,7 +9,6 @@ that are added in a fixed order, not with atomics).
 
 The network description is generic.v3_2_plan's: every shape the reference's constructor accepts.
 """
-import ctypes as C
 import json
 import math
 import os
@@ -20,10 +19,8 @@ import numpy as np
 import torch
 
 from ._lib import R2LError, check, current_stream, dptr, lib
-from .generic import _act_code, _strip, _view, v3_2_plan
-
-ADAM_BETAS = (0.9, 0.999)
-ADAM_EPS = 1e-8
+from .flat_trainer import FlatAdam, init_linears
+from .generic import _act_code, _strip, v3_2_plan
 
 
 def jitter_z_vals(z_vals_dev, n, t_rand=None):
@@ -45,97 +42,7 @@ def jitter_z_vals(z_vals_dev, n, t_rand=None):
 def init_state_dict(plan, seed=None):
     """nn.Linear's default initialisation for every layer of a v3_2_plan, in plan order (what the reference's constructor leaves
     in a freshly built NeRF_v3_2)."""
-    g = torch.random.get_rng_state()
-    if seed is not None:
-        torch.manual_seed(seed)
-    sd = OrderedDict()
-    for p in plan:
-        lin = torch.nn.Linear(p['in_dim'], p['out_dim'])
-        sd[p['key'] + '.weight'], sd[p['key'] + '.bias'] = lin.weight.detach().clone(), lin.bias.detach().clone()
-    if seed is not None:
-        torch.random.set_rng_state(g)
-    return sd
-
-
-class FlatAdam:
-    """What R2LTrainer and train_teacher.NeRFTrainer share: every parameter in one flat device buffer (_param; _grad, _m, _v
-    likewise) cut into per-tensor views by _slices (name -> (offset, count, shape), in the reference's model.parameters() order),
-    one r2l_train_adam launch over the whole buffer, and the state in torch.optim.Adam's format.
-
-    _frozen: names that never receive a gradient (a module the reference builds and its forward never calls).  torch's Adam skips a
-    parameter whose .grad is None: it keeps no state for it and never moves it.  Here their gradient stays zero, which the launch
-    maps to an update of exactly zero with zero moments; the saved state has no entry for them and a loaded state need not."""
-    _frozen = frozenset()
-
-    def _views(self, flat):
-        return OrderedDict((k, flat[o:o + c].view(shape)) for k, (o, c, shape) in self._slices.items())
-
-    def grads(self):
-        self._need_state()
-        return OrderedDict((k, v.detach().clone()) for k, v in self.g.items())
-
-    def _need_state(self):
-        if self._param is None:
-            raise R2LError('the trainer has no weights yet: load_state_dict first')
-
-    def optimizer_state_dict(self):
-        """torch.optim.Adam.state_dict(): parameters indexed in model.parameters() order (weight then bias, layer by layer)."""
-        self._need_state()
-        idx = list(range(len(self._slices)))
-        state = {}
-        if self.t > 0:
-            for i, k in enumerate(self._slices):
-                if k in self._frozen:
-                    continue
-                state[i] = {'step': torch.tensor(float(self.t)), 'exp_avg': self.exp_avg[k].detach().cpu().clone(),
-                            'exp_avg_sq': self.exp_avg_sq[k].detach().cpu().clone()}
-        group = {'lr': float(self.lr), 'betas': ADAM_BETAS, 'eps': ADAM_EPS, 'weight_decay': 0, 'amsgrad': False, 'maximize': False,
-                 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None, 'decoupled_weight_decay': False,
-                 'params': idx}
-        return {'state': state, 'param_groups': [group]}
-
-    def load_optimizer_state_dict(self, osd):
-        self._need_state()
-        groups = osd.get('param_groups', [])
-        n_par = sum(len(g['params']) for g in groups)
-        if n_par != len(self._slices):
-            raise R2LError(f'the optimizer state describes {n_par} parameters, this network has {len(self._slices)}')
-        for g in groups:
-            if tuple(g.get('betas', ADAM_BETAS)) != ADAM_BETAS or g.get('eps', ADAM_EPS) != ADAM_EPS or g.get('weight_decay', 0) != 0 \
-                    or g.get('amsgrad', False):
-                raise R2LError(f"the Adam built here has betas {ADAM_BETAS}, eps {ADAM_EPS}, no weight decay, no amsgrad; the state has "
-                               f"betas {g.get('betas')} eps {g.get('eps')} weight_decay {g.get('weight_decay')} amsgrad {g.get('amsgrad')}")
-        order = [i for g in groups for i in g['params']]
-        state = osd.get('state', {})
-        self._m.zero_()
-        self._v.zero_()
-        steps = set()
-        for pos, k in zip(order, self._slices):
-            st = state.get(pos)
-            if st is None:
-                continue
-            for name, dst in (('exp_avg', self.exp_avg[k]), ('exp_avg_sq', self.exp_avg_sq[k])):
-                if tuple(st[name].shape) != tuple(dst.shape):
-                    raise R2LError(f'optimizer state {pos} ({k}) {name} is {tuple(st[name].shape)}, expected {tuple(dst.shape)}')
-                dst.copy_(st[name].detach().to(torch.float32))
-            steps.add(int(float(st['step'])))
-        n_live = len(self._slices) - len(self._frozen)
-        if len(steps) > 1 or (steps and not n_live <= len(state) <= len(self._slices)):
-            raise R2LError(f'the optimizer state carries step counts {sorted(steps)} over {len(state)} of {n_live} trained parameters: '
-                           f'one flat Adam launch needs one count for all of them')
-        self.t = steps.pop() if steps else 0
-        if groups:
-            self.lr = float(groups[0].get('lr', self.lr))
-        return self
-
-    def adam(self, lr):
-        """One torch.optim.Adam update of every parameter from the gradients in the buffer."""
-        self._need_state()
-        self.t += 1
-        self.lr = float(lr)
-        with torch.cuda.device(self.device):
-            check(lib().r2l_train_adam(dptr(self._param), dptr(self._grad), dptr(self._m), dptr(self._v), self.n_param, float(lr), self.t,
-                                       current_stream()))
+    return init_linears([(p['key'], p['in_dim'], p['out_dim']) for p in plan], seed)
 
 
 class R2LTrainer(FlatAdam):
@@ -145,9 +52,7 @@ class R2LTrainer(FlatAdam):
 
     def __init__(self, near=2., far=6., n_sample=16, L=10, netdepth=88, netwidth=256, layerwise_netwidths='', act='relu',
                  use_residual=True, trial=None, max_rays=1 << 14, device=None, z_vals=None):
-        if not torch.cuda.is_available():
-            raise R2LError('no HIP device visible to torch: training has no CPU fallback')
-        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self._set_device(device, max_rays)
         self.n_sample, self.L = int(n_sample), int(L)
         if not 1 <= self.L <= 16 or self.n_sample < 1:
             raise R2LError(f'n_sample={n_sample} multires={L}')
@@ -156,9 +61,6 @@ class R2LTrainer(FlatAdam):
         self.plan = v3_2_plan(netdepth, netwidth, self.input_dim, 3, layerwise_netwidths, act, use_residual, trial)
         if len(self.plan) == 2 and self.use_residual:
             raise R2LError('an empty body with --use_residual (netdepth < 4) is not built')
-        self.max_rays = int(max_rays)
-        if self.max_rays < 1:
-            raise R2LError(f'max_rays={max_rays}')
         if z_vals is None:       # model/nerf_raybased.py:88-90, on the host as the reference does
             t_vals = torch.linspace(0., 1., steps=self.n_sample)
             z_vals = float(near) * (1 - t_vals) + float(far) * t_vals
@@ -171,27 +73,13 @@ class R2LTrainer(FlatAdam):
                 start = i
             if p.get('block_out'):
                 self._block_start[i] = start
-        # flat layout: weight then bias, layer by layer (model.parameters() order)
-        self._slices = OrderedDict()
-        off = 0
-        for p in self.plan:
-            for kind, shape in (('weight', (p['out_dim'], p['in_dim'])), ('bias', (p['out_dim'],))):
-                cnt = int(np.prod(shape))
-                self._slices[f"{p['key']}.{kind}"] = (off, cnt, shape)
-                off += cnt
-        self.n_param = off
-        self.t = 0                # Adam updates so far
-        self.lr = 0.
-        self._param = None
+        self._set_layout([(p['key'], p['in_dim'], p['out_dim']) for p in self.plan])       # model.parameters() order
 
     # ---- state -------------------------------------------------------------------------------------------------------------
     @property
     def flops_per_ray(self):
         """of the forward pass; a training step is about three times that (g_x and g_W cost one forward each)"""
         return 2 * sum(p['in_dim'] * p['out_dim'] for p in self.plan)
-
-    def state_names(self):
-        return list(self._slices)
 
     def activation_bytes(self, n=None):
         n = self.max_rays if n is None else n
@@ -206,7 +94,7 @@ class R2LTrainer(FlatAdam):
         want = self.activation_bytes() + 4 * (4 * self.n_param + 4 * n * wmax + ws_floats + 8 * n)
         try:
             with torch.cuda.device(dev):
-                self._param, self._grad, self._m, self._v = (torch.zeros(self.n_param, **f32) for _ in range(4))
+                self._allocate_flat()
                 self._acts = [torch.empty((n, p['out_dim']), **f32) for p in self.plan]
                 self._emb = torch.empty((n, self.input_dim), **f32)
                 self._pts = torch.empty((n, 3 * self.n_sample), **f32)
@@ -218,12 +106,10 @@ class R2LTrainer(FlatAdam):
                 self._loss_ws = torch.empty(((n + 255) // 256,), **f32)
                 self._z_dev = self.z_vals.to(dev)
         except (torch.cuda.OutOfMemoryError, RuntimeError) as e:
-            self._param = None
+            self._release_flat()
             raise R2LError(f'cannot allocate the training buffers for {n} rays per step: about {want / 2 ** 30:.1f} GiB (saved layer '
                            f'outputs {self.activation_bytes() / 2 ** 30:.1f} GiB: {len(self.plan)} layers; slab workspace '
                            f'{4 * ws_floats / 2 ** 30:.2f} GiB): {e}. Lower --N_rand or the hard-ray share.') from e
-        self.p, self.g = self._views(self._param), self._views(self._grad)
-        self.exp_avg, self.exp_avg_sq = self._views(self._m), self._views(self._v)
 
     def load_state_dict(self, state_dict):
         sd = _strip(state_dict)
@@ -244,67 +130,31 @@ class R2LTrainer(FlatAdam):
         self._need_state()
         return OrderedDict((k, v.detach().cpu().clone()) for k, v in self.p.items())
 
-    # ---- one step ----------------------------------------------------------------------------------------------------------
-    def _forward_layer(self, i, x, y, res=None, post=None):
-        p = self.plan[i]
-        xp, ldx = _view(x, p['in_dim'])
-        yp, ldy = _view(y, p['out_dim'])
-        rp, ldr = _view(res)
-        pp, ldp = _view(post)
-        check(lib().r2l_linear_forward_dev(dptr(self.p[p['key'] + '.weight']), dptr(self.p[p['key'] + '.bias']), p['out_dim'], p['in_dim'],
-                                           xp, ldx, x.shape[0], yp, ldy, rp, ldr, float(p.get('res_scale', 1.0)), _act_code(p['act']),
-                                           pp, ldp, current_stream()))
+    def checkpoint_networks(self):
+        return pair_networks(self.state_dict())
 
+    # ---- one step ----------------------------------------------------------------------------------------------------------
     def forward(self, emb, n):
         """NeRF_v3_2.forward (model/nerf_raybased.py:539-544) keeping every layer's output; returns rgb [n, 3] (a view)."""
         acts = [a[:n] for a in self._acts]
-        self._forward_layer(0, emb, acts[0])
+        plan = self.plan
+        self._linear(plan[0]['key'], emb, acts[0], _act_code(plan[0]['act']), None, plan[0].get('res_scale', 1.0))
         cur = acts[0]
-        last_body = len(self.plan) - 2
-        for i in range(1, last_body + 1):
-            p = self.plan[i]
-            if p.get('block_in'):
+        last_body = len(plan) - 2
+        for i in range(1, len(plan)):
+            p = plan[i]
+            body = i <= last_body
+            if body and p.get('block_in'):
                 cur = acts[i - 1]
-            self._forward_layer(i, acts[i - 1], acts[i], res=cur if p.get('block_out') else None,
-                                post=acts[0] if (i == last_body and self.use_residual) else None)
-        self._forward_layer(len(self.plan) - 1, acts[-2], acts[-1])
+            self._linear(p['key'], acts[i - 1], acts[i], _act_code(p['act']), cur if body and p.get('block_out') else None,
+                         p.get('res_scale', 1.0), acts[0] if (i == last_body and self.use_residual) else None)
         return acts[-1]
-
-    def _grad_weight(self, i, gz, x):
-        p = self.plan[i]
-        n = x.shape[0]
-        zp, ldz = _view(gz, p['out_dim'])
-        xp, ldx = _view(x, p['in_dim'])
-        check(lib().r2l_train_grad_weight(zp, ldz, xp, ldx, n, p['out_dim'], p['in_dim'], dptr(self.g[p['key'] + '.weight']),
-                                          dptr(self.g[p['key'] + '.bias']), dptr(self._ws), self._ws.numel(), current_stream()))
-
-    def _grad_input(self, i, gz, gx, accumulate):
-        p = self.plan[i]
-        zp, ldz = _view(gz, p['out_dim'])
-        xp, ldx = _view(gx, p['in_dim'])
-        check(lib().r2l_train_grad_input(zp, ldz, gz.shape[0], dptr(self.p[p['key'] + '.weight']), p['out_dim'], p['in_dim'], xp, ldx,
-                                         1 if accumulate else 0, current_stream()))
-
-    def _act_backward(self, i, g_y, y, post, scale, g_z, g_res, res_acc, g_post):
-        p = self.plan[i]
-        w = p['out_dim']
-        gp, ldg = _view(g_y, w)
-        yp, ldy = _view(y, w)
-        pp, ldp = _view(post)
-        zp, ldz = _view(g_z, w)
-        rp, ldr = _view(g_res)
-        qp, ldq = _view(g_post)
-        check(lib().r2l_train_act_backward(gp, ldg, yp, ldy, pp, ldp, y.shape[0], w, _act_code(p['act']), float(scale), zp, ldz, rp, ldr,
-                                           1 if res_acc else 0, qp, ldq, 0, current_stream()))
 
     def embed(self, rays_o, rays_d, perturb=1., t_rand=None):
         """positional_embedder(point_sampler.sample_train(rays_o, rays_d, perturb)) into the trainer's buffer: [n, input_dim]"""
         self._need_state()
         n = rays_o.shape[0]
-        if n > self.max_rays:
-            raise R2LError(f'{n} rays in a step, the buffers were allocated for max_rays = {self.max_rays}')
-        ro = rays_o.to(self.device, torch.float32).contiguous()
-        rd = rays_d.to(self.device, torch.float32).contiguous()
+        ro, rd = self._on_device(n, rays_o=rays_o, rays_d=rays_d)
         pts, emb = self._pts[:n], self._emb[:n]
         with torch.cuda.device(self.device):
             if perturb > 0.:
@@ -323,11 +173,7 @@ class R2LTrainer(FlatAdam):
     def forward_backward_embedded(self, emb, target):
         self._need_state()
         n = emb.shape[0]
-        if n > self.max_rays:
-            raise R2LError(f'{n} rays in a step, the buffers were allocated for max_rays = {self.max_rays}')
-        tgt = target.to(self.device, torch.float32).contiguous()
-        if tuple(tgt.shape) != (n, 3):
-            raise R2LError(f'target is {tuple(tgt.shape)}, expected {(n, 3)}')
+        tgt, = self._on_device(n, target=target)
         plan, nl = self.plan, len(self.plan)
         last_body = nl - 2
         with torch.cuda.device(self.device):
@@ -336,11 +182,10 @@ class R2LTrainer(FlatAdam):
             R, Y, Z, P = (b[:n] for b in self._gbuf)
             # loss, and through the tail's sigmoid: the tail layer's g_z
             gz = self._gtail[:n]
-            check(lib().r2l_train_mse_loss(dptr(rgb), dptr(tgt), n, 1, dptr(gz), dptr(self._err[:n]), dptr(self._loss), dptr(self._loss_ws),
-                                           self._loss_ws.numel(), current_stream()))
-            self._grad_weight(nl - 1, gz, acts[-2])
+            self._mse_loss(rgb, tgt, 1, gz, self._loss, self._err[:n])
+            self._grad_weight(plan[-1]['key'], gz, acts[-2])
             g_y = R[:, :plan[-1]['in_dim']]
-            self._grad_input(nl - 1, gz, g_y, False)
+            self._grad_input(plan[-1]['key'], gz, g_y, False)
             # body, last layer first.  `stream`: the buffer the gradient of the open block's input is collected in (g_res, then
             # the g_x of the block's first layer on top); P: the same for the head's output under --use_residual (g_post)
             stream = None
@@ -356,21 +201,21 @@ class R2LTrainer(FlatAdam):
                         g_res, res_acc = g_y, False                  # in place: g_u over g_y
                     stream = g_res
                 z = Z[:, :w_out]
-                self._act_backward(i, g_y, acts[i], acts[0] if has_post else None, p.get('res_scale', 1.0) if has_res else 1.0, z,
-                                   g_res, res_acc, P[:, :w_out] if has_post else None)
-                self._grad_weight(i, z, acts[i - 1])
+                self._act_backward(p['key'], g_y, acts[i], z, _act_code(p['act']), acts[0] if has_post else None,
+                                   p.get('res_scale', 1.0) if has_res else 1.0, g_res, res_acc, P[:, :w_out] if has_post else None)
+                self._grad_weight(p['key'], z, acts[i - 1])
                 if p.get('block_in'):
                     dst, acc = stream, True
                 elif i == 1 and self.use_residual:
                     dst, acc = P[:, :w_in], True
                 else:
                     dst, acc = Y[:, :w_in], False
-                self._grad_input(i, z, dst, acc)
+                self._grad_input(p['key'], z, dst, acc)
                 g_y = dst
             # head: no g_x (the embedding has no parameters)
             z = Z[:, :plan[0]['out_dim']]
-            self._act_backward(0, g_y, acts[0], None, 1.0, z, None, False, None)
-            self._grad_weight(0, z, emb)
+            self._act_backward(plan[0]['key'], g_y, acts[0], z, _act_code(plan[0]['act']))
+            self._grad_weight(plan[0]['key'], z, emb)
         return self._loss
 
     def step(self, rays_o, rays_d, target, lr, perturb=1., t_rand=None):
@@ -394,10 +239,7 @@ class R2LTrainer(FlatAdam):
         the loss and the per-ray error are not touched."""
         self._need_state()
         n = rays_o.shape[0]
-        ro = rays_o.to(self.device, torch.float32).contiguous()
-        rd = rays_d.to(self.device, torch.float32).contiguous()
-        if tuple(ro.shape) != (n, 3) or tuple(rd.shape) != (n, 3):
-            raise R2LError(f'rays_o / rays_d are {tuple(ro.shape)} / {tuple(rd.shape)}, expected {(n, 3)}')
+        ro, rd = self._on_device(n, limit=False, rays_o=rays_o, rays_d=rays_d)
         if out is None:
             out = torch.empty((n, 3), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
@@ -491,21 +333,84 @@ def _infinite_order(n):
             i = 0
 
 
+def pair_networks(coarse, fine=None):
+    """the checkpoint's network entries of a coarse / fine pair of state dicts (main.py:1531-1533)"""
+    nets = {'network_fn_state_dict': dict(coarse)}
+    if fine is not None:
+        nets['network_fine_state_dict'] = dict(fine)
+    return nets
+
+
 def save_train_checkpoint(path, trainer, global_step, best_psnr=0, best_psnr_step=0):
     """The reference's schema (main.py:1516-1542) with the optimizer's state; without the pickled module, which the reference
     only reads when it is there (main.py:484)."""
-    fine = None
-    if hasattr(trainer, 'state_dicts'):        # the teacher's pair: network_fine_state_dict beside it (main.py:1531-1533)
-        coarse, fine = trainer.state_dicts()
-    else:
-        coarse = trainer.state_dict()
+    # a trainer names the networks of its checkpoint; an object that only offers the teacher's state_dicts() pair is read as that
+    nets = trainer.checkpoint_networks() if hasattr(trainer, 'checkpoint_networks') else pair_networks(*trainer.state_dicts())
     to_save = {'global_step': int(global_step), 'best_psnr': best_psnr, 'best_psnr_step': best_psnr_step,
-               'network_fn_state_dict': dict(coarse), 'optimizer_state_dict': trainer.optimizer_state_dict()}
-    if fine is not None:
-        to_save['network_fine_state_dict'] = dict(fine)
+               'network_fn_state_dict': nets['network_fn_state_dict'], 'optimizer_state_dict': trainer.optimizer_state_dict()}
+    to_save.update(nets)          # the teacher's network_fine_state_dict goes behind them (main.py:1531-1533)
     tmp = path + '.tmp'
     torch.save(to_save, tmp)
     os.replace(tmp, path)
+    return path
+
+
+def refuse_negative_i_testset(args):
+    if args.i_testset < 0:
+        raise SystemExit(f'--i_testset {args.i_testset}: a positive interval, or 0 for no test renders')
+
+
+def run_iterations(args, trainer, start, best, weights_dir, log, *, draw, after_step, test_pass=None,
+                   ckpt_name=lambda it: 'ckpt.tar', step_args={}):
+    """Iterations start + 1 .. N_iters of main.py:1136-1513 on either trainer: the learning rate, the step, the [TRAIN] line, the
+    test renders every --i_testset iterations (0: none) with the best checkpoint and the [TEST] line, the periodic and the final
+    checkpoint.  Returns the path of the last checkpoint written.  What differs between the trainers comes in as
+      draw(i)                   -> (rays_o, rays_d, target) of iteration i on the device; its time is the line's data_time
+      after_step(batch, second) -> the mse the line's psnr is of, or None for the loss; second: what trainer.step returned second
+      test_pass(i)              -> (test_psnr, test_psnr_v2, further fields of the [TEST] line, a line to log after it or None)
+      ckpt_name(i)              -> the periodic checkpoint's file name
+    best: (best_psnr, best_psnr_step) so far; step_args: passed on to trainer.step beside perturb."""
+    from .frontend import mse2psnr
+    best_psnr, best_psnr_step = best
+    save = lambda name, it: save_train_checkpoint(os.path.join(weights_dir, name), trainer, it, best_psnr, best_psnr_step)
+    hist_psnr = 0.
+    path = None
+    log('Begin training')
+    for i in range(start + 1, args.N_iters + 1):
+        t0 = time.time()
+        lr = learning_rate(i, args.lrate, args.lrate_decay, args.warmup_lr)
+        batch = draw(i)
+        t_data = time.time() - t0
+        loss, second = trainer.step(*batch, lr, perturb=args.perturb, **step_args)
+        mse = after_step(batch, second)
+        loss_v = float(loss.item())
+        t_batch = time.time() - t0
+        if not math.isfinite(loss_v):
+            raise R2LError(f'the loss is {loss_v} at iteration {i} (LR {lr:.10f})')
+        psnr = mse2psnr(loss_v if mse is None else mse)
+        hist_psnr = psnr if i == start + 1 else hist_psnr * 0.95 + psnr * 0.05
+        if i % args.i_print == 0:
+            log(f'[TRAIN] Iter {i} data_time {t_data:.4f} batch_time {t_batch:.4f} loss {loss_v:.6f} psnr {psnr:.4f} hist_psnr {hist_psnr:.4f} '
+                f'LR {lr:.10f}')
+        if test_pass is not None and args.i_testset and i % args.i_testset == 0:      # main.py:1442-1471
+            log(f'Iter {i} Testing...')
+            t_ = time.time()
+            test_psnr, test_psnr_v2, fields, after = test_pass(i)
+            t_test = time.time() - t_
+            if test_psnr_v2 > best_psnr:                      # main.py:1458
+                best_psnr, best_psnr_step = test_psnr_v2, i
+                best_path = save('ckpt_best.tar', i)
+                log(f'Iter {i} Save the best checkpoint: "{best_path}".')
+            log(f'[TEST] Iter {i} TestPSNR {test_psnr:.4f} TestPSNRv2 {test_psnr_v2:.4f} BestPSNRv2 {best_psnr:.4f} (Iter {best_psnr_step}) '
+                f'{fields}TrainHistPSNR {hist_psnr:.4f} LR {lr:.8f} Time {t_test:.1f}s')
+            if after:
+                log(after)
+        if i % args.i_weights == 0:
+            path = save(ckpt_name(i), i)
+            log(f'Iter {i} Save checkpoint: "{path}".')
+    if args.N_iters > start and args.N_iters % args.i_weights != 0:
+        path = save(ckpt_name(args.N_iters), args.N_iters)
+        log(f'Iter {args.N_iters} Save checkpoint: "{path}".')
     return path
 
 
@@ -591,7 +496,7 @@ def _train(args, log, engines):
     """main.py without --render_only for --model_name R2L / nerf_v3.2, --data_mode rays; with --kd_online the rays of every step are
     rendered by the teacher on the device (online.py) instead of read from shards, and everything behind them is the same code."""
     from .create_data import BlenderDataset_v2
-    from .frontend import load_checkpoint, mse2psnr
+    from .frontend import load_checkpoint
     online = bool(getattr(args, 'kd_online', False))
     if online:                 # every step's rays from the teacher (online.py) instead of shards
         from .online import check_online_args, source_from_args
@@ -610,8 +515,7 @@ def _train(args, log, engines):
     batch_size = args.N_rand * split
     pool = HardRayPool(args.hard_ratio, args.hard_mul) if parse_hard_ratio(args.hard_ratio) else None
     n_hard_out = pool.counts(batch_size)[1] if pool else 0
-    if args.i_testset < 0:
-        raise SystemExit(f'--i_testset {args.i_testset}: a positive interval, or 0 for no test renders')
+    refuse_negative_i_testset(args)
     trainer = trainer_from_args(args, batch_size + n_hard_out)
     dev = trainer.device
     if online:
@@ -649,15 +553,9 @@ def _train(args, log, engines):
         log('Testing pretrained...')
         _, misc = eval_test_split(trainer, test)
         log(f"Pretrained test: TestPSNR {misc['test_psnr']:.4f} TestPSNRv2 {misc['test_psnr_v2']:.4f}")
-    ckpt_name = lambda it: f'ckpt_{it}.tar' if args.save_intermediate_models else 'ckpt.tar'       # main.py:1510
     order = None if online else _infinite_order(len(dataset))
-    hist_psnr = 0.
-    t_data = t_batch = 0.
-    path = None
-    log('Begin training')
-    for i in range(start + 1, args.N_iters + 1):
-        t0 = time.time()
-        lr = learning_rate(i, args.lrate, args.lrate_decay, args.warmup_lr)
+
+    def draw(i):
         if online:
             rays_o, rays_d, target = source.batch(i, batch_size)
         else:
@@ -669,36 +567,17 @@ def _train(args, log, engines):
                 rays_o, rays_d, target = (torch.cat([a, picked[:, 3 * k:3 * k + 3]], 0) for k, a in enumerate((rays_o, rays_d, target)))
         if online:
             torch.cuda.synchronize(dev)       # data_time contains the teacher's render
-        t_data = time.time() - t0
-        loss, err = trainer.step(rays_o, rays_d, target, lr, perturb=args.perturb)
+        return rays_o, rays_d, target
+
+    def after_step(batch, err):               # the psnr is the loss's own
         if pool is not None:
-            pool.update(err, rays_o, rays_d, target, batch_size)
-        loss_v = float(loss.item())
-        t_batch = time.time() - t0
-        psnr = mse2psnr(loss_v)
-        if not math.isfinite(loss_v):
-            raise R2LError(f'the loss is {loss_v} at iteration {i} (LR {lr:.10f})')
-        hist_psnr = psnr if i == start + 1 else hist_psnr * 0.95 + psnr * 0.05
-        if i % args.i_print == 0:
-            log(f'[TRAIN] Iter {i} data_time {t_data:.4f} batch_time {t_batch:.4f} loss {loss_v:.6f} psnr {psnr:.4f} hist_psnr {hist_psnr:.4f} '
-                f'LR {lr:.10f}')
-        if test is not None and args.i_testset and i % args.i_testset == 0:      # main.py:1442-1471
-            testsavedir = os.path.join(expdir, f'testset_iter{i}')
-            log(f'Iter {i} Testing...')
-            t_ = time.time()
-            _, misc = eval_test_split(trainer, test, savedir=testsavedir)
-            t_test = time.time() - t_
-            if misc['test_psnr_v2'] > best_psnr:              # main.py:1458
-                best_psnr, best_psnr_step = misc['test_psnr_v2'], i
-                best = save_train_checkpoint(os.path.join(weights_dir, 'ckpt_best.tar'), trainer, i, best_psnr, best_psnr_step)
-                log(f'Iter {i} Save the best checkpoint: "{best}".')
-            log(f"[TEST] Iter {i} TestPSNR {misc['test_psnr']:.4f} TestPSNRv2 {misc['test_psnr_v2']:.4f} BestPSNRv2 {best_psnr:.4f} "
-                f"(Iter {best_psnr_step}) TestSSIM {misc['test_ssim']:.4f} TrainHistPSNR {hist_psnr:.4f} LR {lr:.8f} Time {t_test:.1f}s")
-            log(f'Saved rendered test images: "{testsavedir}"')
-        if i % args.i_weights == 0:
-            path = save_train_checkpoint(os.path.join(weights_dir, ckpt_name(i)), trainer, i, best_psnr, best_psnr_step)
-            log(f'Iter {i} Save checkpoint: "{path}".')
-    if args.N_iters > start and args.N_iters % args.i_weights != 0:
-        path = save_train_checkpoint(os.path.join(weights_dir, ckpt_name(args.N_iters)), trainer, args.N_iters, best_psnr, best_psnr_step)
-        log(f'Iter {args.N_iters} Save checkpoint: "{path}".')
-    return path
+            pool.update(err, *batch, batch_size)
+
+    def test_pass(i):                         # main.py:1442-1456
+        testsavedir = os.path.join(expdir, f'testset_iter{i}')
+        _, misc = eval_test_split(trainer, test, savedir=testsavedir)
+        return misc['test_psnr'], misc['test_psnr_v2'], f"TestSSIM {misc['test_ssim']:.4f} ", f'Saved rendered test images: "{testsavedir}"'
+
+    return run_iterations(args, trainer, start, (best_psnr, best_psnr_step), weights_dir, log, draw=draw, after_step=after_step,
+                          test_pass=test_pass if test is not None else None,
+                          ckpt_name=lambda it: f'ckpt_{it}.tar' if args.save_intermediate_models else 'ckpt.tar')       # main.py:1510

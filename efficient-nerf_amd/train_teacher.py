@@ -3,7 +3,7 @@ render_rays, main.py:624-756, under autograd plus torch.optim.Adam): both networ
 volume-rendering scans and their backward pass, the two rgb losses and Adam as launches of the library's fp32 kernels
 (csrc/r2l_generic.hip, r2l_train.hip, nerf_kernels.hip, nerf_train.hip; include/r2l_hip.h).
 
-NeRFTrainer holds the coarse network's parameters, then the fine one's, in one flat device buffer (train.FlatAdam), and the
+NeRFTrainer holds the coarse network's parameters, then the fine one's, in one flat device buffer (flat_trainer.FlatAdam), and the
 saved output of every layer of both passes for the backward pass.  torch supplies the buffers, the stream and the random draws
 (t_rand, u, the density noise); every number of a step is computed by the library in exact fp32, and a step is bit-identical from
 run to run (no float atomics anywhere).
@@ -11,19 +11,17 @@ run to run (no float atomics anywhere).
 The networks are generic.nerf_plan's: every pair create_nerf builds (main.py:407-453).  The reference's two torch.cat inputs are
 column slices of wider buffers, as in generic._NeRFNet.forward.
 """
-import math
 import os
-import time
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
 from ._lib import R2LError, check, current_stream, dptr, lib
+from .flat_trainer import ACT_NONE, ACT_RELU, FlatAdam, init_linears
 from .generic import _strip, _view, nerf_plan
-from .train import FlatAdam, jitter_z_vals, learning_rate, save_train_checkpoint
+from .train import jitter_z_vals, pair_networks, refuse_negative_i_testset, run_iterations
 
-ACT_NONE, ACT_RELU = 0, 1
 SKIPS = (4,)
 PREFIXES = ('network_fn', 'network_fine')
 
@@ -56,13 +54,12 @@ class NeRFTrainer(FlatAdam):
     has none for a parameter whose .grad is None, and a state with or without such entries loads.
 
     max_rays: the largest batch a step may carry (the buffers are allocated once, at load_state_dicts)."""
+    _min_rays = 1
 
     def __init__(self, near=2., far=6., N_samples=64, N_importance=128, multires=10, multires_views=4, i_embed=0, netdepth=8,
                  netwidth=256, netdepth_fine=8, netwidth_fine=256, use_viewdirs=True, white_bkgd=False, lindisp=False,
                  max_rays=1024, device=None):
-        if not torch.cuda.is_available():
-            raise R2LError('no HIP device visible to torch: training has no CPU fallback')
-        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self._set_device(device, max_rays)
         self.near, self.far = float(near), float(far)
         self.N_samples, self.N_importance = int(N_samples), int(N_importance)
         self.multires, self.multires_views, self.i_embed = int(multires), int(multires_views), int(i_embed)
@@ -75,9 +72,6 @@ class NeRFTrainer(FlatAdam):
         self.input_ch_views = 0 if not self.use_viewdirs else (3 if self.i_embed == -1 else 3 * (2 * self.multires_views + 1))
         self.output_ch = 5 if self.N_importance > 0 else 4          # main.py:426
         self.raw_ch = 4 if self.use_viewdirs else self.output_ch
-        self.max_rays = int(max_rays)
-        if self.max_rays < 1:
-            raise R2LError(f'max_rays={max_rays}')
         self.nets = [_Net(PREFIXES[0], int(netdepth), int(netwidth), self.N_samples)]
         if self.N_importance > 0:
             self.nets.append(_Net(PREFIXES[1], int(netdepth_fine), int(netwidth_fine), self.N_samples + self.N_importance))
@@ -94,21 +88,10 @@ class NeRFTrainer(FlatAdam):
         nr, fr = torch.tensor([self.near]), torch.tensor([self.far])
         z = nr * (1. - t) + fr * t if not self.lindisp else 1. / (1. / nr * (1. - t) + 1. / fr * t)
         self.z_coarse = z.to(torch.float32).contiguous()
-        # flat layout: the coarse network, then the fine one; weight then bias, module by module in creation order
-        self._slices = OrderedDict()
-        off = 0
-        for net in self.nets:
-            for k, (i, o) in net.layers.items():
-                for kind, shape in (('weight', (o, i)), ('bias', (o,))):
-                    cnt = int(np.prod(shape))
-                    self._slices[f'{net.prefix}.{k}.{kind}'] = (off, cnt, shape)
-                    off += cnt
-        self.n_param = off
+        # flat layout: the coarse network, then the fine one; module by module in creation order
+        self._set_layout([(f'{net.prefix}.{k}', i, o) for net in self.nets for k, (i, o) in net.layers.items()])
         if not self.use_viewdirs:
             self._frozen = frozenset(f'{net.prefix}.views_linears.0.{kind}' for net in self.nets for kind in ('weight', 'bias'))
-        self.t = 0
-        self.lr = 0.
-        self._param = None
         self.last = {}
 
     # ---- state -------------------------------------------------------------------------------------------------------------
@@ -117,9 +100,6 @@ class NeRFTrainer(FlatAdam):
         """of the two forward passes; a training step is about three times that (g_x and g_W cost one forward each)"""
         return 2 * sum(net.S * sum(i * o for k, (i, o) in net.layers.items() if self.use_viewdirs or k != 'views_linears.0')
                        for net in self.nets)
-
-    def state_names(self):
-        return list(self._slices)
 
     def _per_point_floats(self, net):
         """saved layer outputs and inputs of one point of one network"""
@@ -149,7 +129,7 @@ class NeRFTrainer(FlatAdam):
                            f'Lower --N_rand.')
         try:
             with torch.cuda.device(dev):
-                self._param, self._grad, self._m, self._v = (torch.zeros(self.n_param, **f32) for _ in range(4))
+                self._allocate_flat()
                 for net in self.nets:
                     m, W = n * net.S, net.W
                     net.pts = torch.empty((m, 3), **f32)
@@ -176,28 +156,15 @@ class NeRFTrainer(FlatAdam):
                 self._weights = torch.empty((n, self.N_samples), **f32)
                 self._z_dev = self.z_coarse.to(dev)
         except (torch.cuda.OutOfMemoryError, RuntimeError) as e:
-            self._param = None
+            self._release_flat()
             for net in self.nets:
                 net.__dict__ = {k: v for k, v in net.__dict__.items() if not torch.is_tensor(v) and k != 'acts'}
             raise R2LError(f'cannot allocate the training buffers for {n} rays per step: {sizes}: {e}. Lower --N_rand.') from e
-        self.p, self.g = self._views(self._param), self._views(self._grad)
-        self.exp_avg, self.exp_avg_sq = self._views(self._m), self._views(self._v)
 
     def init_state_dicts(self, seed=None):
         """nn.Linear's default initialisation of every module, in creation order: (coarse, fine or None)"""
-        g = torch.random.get_rng_state()
-        if seed is not None:
-            torch.manual_seed(seed)
-        out = []
-        for net in self.nets:
-            sd = OrderedDict()
-            for k, (i, o) in net.layers.items():
-                lin = torch.nn.Linear(i, o)
-                sd[k + '.weight'], sd[k + '.bias'] = lin.weight.detach().clone(), lin.bias.detach().clone()
-            out.append(sd)
-        if seed is not None:
-            torch.random.set_rng_state(g)
-        return out[0], (out[1] if len(out) > 1 else None)
+        sd = init_linears([(name, i, o) for name, (i, o) in self._dims.items()], seed)
+        return self._split(sd, lambda v: v)
 
     def load_state_dicts(self, network_fn_state_dict, network_fine_state_dict=None):
         sds = [_strip(network_fn_state_dict)]
@@ -220,58 +187,28 @@ class NeRFTrainer(FlatAdam):
                     self.p[f'{net.prefix}.{k}.{kind}'].copy_(torch.as_tensor(sd[f'{k}.{kind}']).detach().to(torch.float32))
         return self
 
-    def _split(self, views, host):
+    def _split(self, named, copy):
+        """an OrderedDict keyed by parameter name as (coarse, fine or None) without the networks' prefixes"""
         out = []
         for net in self.nets:
             cut = len(net.prefix) + 1
-            out.append(OrderedDict((k[cut:], (v.detach().cpu().clone() if host else v.detach().clone())) for k, v in views.items()
-                                   if k.startswith(net.prefix + '.')))
+            out.append(OrderedDict((k[cut:], copy(v)) for k, v in named.items() if k.startswith(net.prefix + '.')))
         return out[0], (out[1] if len(out) > 1 else None)
 
     def state_dicts(self):
         """(network_fn_state_dict, network_fine_state_dict or None) on the host, keyed as the reference's checkpoint"""
         self._need_state()
-        return self._split(self.p, True)
+        return self._split(self.p, lambda v: v.detach().cpu().clone())
 
     def grads(self):
         """the gradients of the last forward_backward, as state_dicts() is keyed: (coarse, fine or None), on the device"""
         self._need_state()
-        return self._split(self.g, False)
+        return self._split(self.g, lambda v: v.detach().clone())
 
-    # ---- launches ----------------------------------------------------------------------------------------------------------
-    def _w(self, net, key):
-        return self.p[f'{net.prefix}.{key}.weight'], self.p[f'{net.prefix}.{key}.bias']
+    def checkpoint_networks(self):
+        return pair_networks(*self.state_dicts())
 
-    def _linear(self, net, key, x, y, act):
-        i, o = net.layers[key]
-        w, b = self._w(net, key)
-        xp, ldx = _view(x, i)
-        yp, ldy = _view(y, o)
-        check(lib().r2l_linear_forward_dev(dptr(w), dptr(b), o, i, xp, ldx, x.shape[0], yp, ldy, None, 0, 1.0, act, None, 0,
-                                           current_stream()))
-
-    def _grad_weight(self, net, key, gz, x):
-        i, o = net.layers[key]
-        zp, ldz = _view(gz, o)
-        xp, ldx = _view(x, i)
-        check(lib().r2l_train_grad_weight(zp, ldz, xp, ldx, x.shape[0], o, i, dptr(self.g[f'{net.prefix}.{key}.weight']),
-                                          dptr(self.g[f'{net.prefix}.{key}.bias']), dptr(self._ws), self._ws.numel(), current_stream()))
-
-    def _grad_input(self, net, key, gz, gx, accumulate):
-        i, o = net.layers[key]
-        zp, ldz = _view(gz, o)
-        xp, ldx = _view(gx, i)
-        check(lib().r2l_train_grad_input(zp, ldz, gz.shape[0], dptr(self._w(net, key)[0]), o, i, xp, ldx, 1 if accumulate else 0,
-                                         current_stream()))
-
-    def _relu_backward(self, g_y, y, g_z):
-        w = y.shape[1]
-        gp, ldg = _view(g_y, w)
-        yp, ldy = _view(y, w)
-        zp, ldz = _view(g_z, w)
-        check(lib().r2l_train_act_backward(gp, ldg, yp, ldy, None, 0, y.shape[0], w, ACT_RELU, 1.0, zp, ldz, None, 0, 0, None, 0, 0,
-                                           current_stream()))
-
+    # ---- launches beside FlatAdam's ----------------------------------------------------------------------------------------
     def _embed(self, x, L, out):
         """get_embedder(L, i_embed) of x [m, 3] into the view `out`"""
         if self.i_embed == -1:
@@ -294,25 +231,25 @@ class NeRFTrainer(FlatAdam):
     def _net_forward(self, net, ro, rd, viewdirs, z):
         """network_query_fn(rays_o + rays_d * z, viewdirs, network) (main.py:65-87, 701-707) keeping every layer's output:
         raw [n * S, raw_ch] (a view)"""
-        n, S, W, ic = ro.shape[0], net.S, net.W, self.input_ch
+        n, S, W, ic, pre = ro.shape[0], net.S, net.W, self.input_ch, net.prefix + '.'
         m = n * S
         pts, cat, raw = net.pts[:m], net.cat[:m], net.raw[:m]
         check(lib().r2l_sample_points(dptr(ro), dptr(rd), n, dptr(z), S, 1, dptr(pts), current_stream()))
         self._embed(pts, self.multires, cat[:, :ic])
         io = self._layer_io(net, m)
         for i, (x, y) in enumerate(io):
-            self._linear(net, f'pts_linears.{i}', x, y, ACT_RELU)
+            self._linear(f'{pre}pts_linears.{i}', x, y, ACT_RELU)
         h = io[-1][1]
         if not self.use_viewdirs:
-            self._linear(net, 'output_linear', h, raw, ACT_NONE)
+            self._linear(pre + 'output_linear', h, raw, ACT_NONE)
             return raw
         views, hv = net.views[:m], net.hv[:m]
         dirs = viewdirs[:, None, :].expand(n, S, 3).reshape(m, 3).contiguous()        # main.py:76-77
         self._embed(dirs, self.multires_views, views[:, W:])
-        self._linear(net, 'alpha_linear', h, raw[:, 3:4], ACT_NONE)
-        self._linear(net, 'feature_linear', h, views[:, :W], ACT_NONE)
-        self._linear(net, 'views_linears.0', views, hv, ACT_RELU)
-        self._linear(net, 'rgb_linear', hv, raw[:, :3], ACT_NONE)
+        self._linear(pre + 'alpha_linear', h, raw[:, 3:4], ACT_NONE)
+        self._linear(pre + 'feature_linear', h, views[:, :W], ACT_NONE)
+        self._linear(pre + 'views_linears.0', views, hv, ACT_RELU)
+        self._linear(pre + 'rgb_linear', hv, raw[:, :3], ACT_NONE)
         return raw
 
     def _scan_forward(self, net, raw, z, rd, noise, weights):
@@ -335,7 +272,7 @@ class NeRFTrainer(FlatAdam):
 
     def _net_backward(self, net, raw4, z, rd, noise, n):
         """from net.g_rgb (the loss's gradient at rgb_map) through the scan and the network into the flat gradient buffer"""
-        S, W, ic = net.S, net.W, self.input_ch
+        S, W, ic, pre = net.S, net.W, self.input_ch, net.prefix + '.'
         m = n * S
         mat = lambda flat, cols: flat[:m * cols].view(m, cols)
         g_raw = self._scan_backward(net, raw4, z, rd, noise, mat(self._g_raw, 4))
@@ -345,31 +282,31 @@ class NeRFTrainer(FlatAdam):
         if self.use_viewdirs:
             views, hv = net.views[:m], net.hv[:m]
             g_hv, g_zv, g_views = mat(self._ghv, W // 2), mat(self._gzv, W // 2), mat(self._gviews, W + self.input_ch_views)
-            self._grad_weight(net, 'rgb_linear', g_raw[:, :3], hv)
-            self._grad_input(net, 'rgb_linear', g_raw[:, :3], g_hv, False)
-            self._relu_backward(g_hv, hv, g_zv)
-            self._grad_weight(net, 'views_linears.0', g_zv, views)
-            self._grad_input(net, 'views_linears.0', g_zv, g_views, False)
-            self._grad_weight(net, 'feature_linear', g_views[:, :W], h)
-            self._grad_input(net, 'feature_linear', g_views[:, :W], g_h, False)
-            self._grad_weight(net, 'alpha_linear', g_raw[:, 3:4], h)             # alpha and feature both read h: their g_h add up
-            self._grad_input(net, 'alpha_linear', g_raw[:, 3:4], g_h, True)
+            self._grad_weight(pre + 'rgb_linear', g_raw[:, :3], hv)
+            self._grad_input(pre + 'rgb_linear', g_raw[:, :3], g_hv, False)
+            self._act_backward(pre + 'views_linears.0', g_hv, hv, g_zv)
+            self._grad_weight(pre + 'views_linears.0', g_zv, views)
+            self._grad_input(pre + 'views_linears.0', g_zv, g_views, False)
+            self._grad_weight(pre + 'feature_linear', g_views[:, :W], h)
+            self._grad_input(pre + 'feature_linear', g_views[:, :W], g_h, False)
+            self._grad_weight(pre + 'alpha_linear', g_raw[:, 3:4], h)             # alpha and feature both read h: their g_h add up
+            self._grad_input(pre + 'alpha_linear', g_raw[:, 3:4], g_h, True)
         else:
             g_out = g_raw
             if self.raw_ch != 4:                      # the unused fifth output: its column of g_out stays zero
                 g_out = mat(self._g_out, self.raw_ch)
                 g_out[:, :4].copy_(g_raw)
-            self._grad_weight(net, 'output_linear', g_out, h)
-            self._grad_input(net, 'output_linear', g_out, g_h, False)
+            self._grad_weight(pre + 'output_linear', g_out, h)
+            self._grad_input(pre + 'output_linear', g_out, g_h, False)
         g_y, cur, other = g_h, self._GA, self._GB
         g_z = mat(self._Z, W)
         for i in range(net.D - 1, -1, -1):
             x, y = io[i]
-            self._relu_backward(g_y, y, g_z)
-            self._grad_weight(net, f'pts_linears.{i}', g_z, x)
+            self._act_backward(f'{pre}pts_linears.{i}', g_y, y, g_z)
+            self._grad_weight(f'{pre}pts_linears.{i}', g_z, x)
             if i > 0:                                 # the embedding has no parameters: no g_x for layer 0
                 g_x = mat(other, x.shape[1])
-                self._grad_input(net, f'pts_linears.{i}', g_z, g_x, False)
+                self._grad_input(f'{pre}pts_linears.{i}', g_z, g_x, False)
                 g_y = g_x[:, ic:] if (i - 1) in SKIPS else g_x     # behind a skip layer x = [input_pts | h]
                 cur, other = other, cur
 
@@ -396,14 +333,8 @@ class NeRFTrainer(FlatAdam):
         from .teacher import merge_sorted, sample_pdf
         self._need_state()
         n = rays_o.shape[0]
-        if n > self.max_rays or n < 1:
-            raise R2LError(f'{n} rays in a step, the buffers were allocated for max_rays = {self.max_rays}')
         dev = self.device
-        ro = rays_o.to(dev, torch.float32).contiguous()
-        rd = rays_d.to(dev, torch.float32).contiguous()
-        tgt = target.to(dev, torch.float32).contiguous()
-        if tuple(ro.shape) != (n, 3) or tuple(rd.shape) != (n, 3) or tuple(tgt.shape) != (n, 3):
-            raise R2LError(f'rays_o / rays_d / target are {tuple(ro.shape)} / {tuple(rd.shape)} / {tuple(tgt.shape)}, expected {(n, 3)}')
+        ro, rd, tgt = self._on_device(n, rays_o=rays_o, rays_d=rays_d, target=target)
         S0, Ni = self.N_samples, self.N_importance
         fine = Ni > 0
         noises = [None, None]
@@ -437,9 +368,7 @@ class NeRFTrainer(FlatAdam):
                 self.last['rgb'] = c.rgb[:n]
             top = f if fine else c
             for net in self.nets:                     # img2mse and its gradient at rgb_map; the per-ray error of the final rgb
-                check(lib().r2l_train_mse_loss(dptr(net.rgb[:n]), dptr(tgt), n, 0, dptr(net.g_rgb[:n]),
-                                               dptr(self._err[:n]) if net is top else None, dptr(net.loss), dptr(self._loss_ws),
-                                               self._loss_ws.numel(), current_stream()))
+                self._mse_loss(net.rgb[:n], tgt, 0, net.g_rgb[:n], net.loss, self._err[:n] if net is top else None)
             if fine:
                 self._net_backward(f, raw1_4, z1, rd, noises[1], n)
             self._net_backward(c, raw0_4, z0, rd, noises[0], n)
@@ -502,6 +431,7 @@ def check_supported(args, start=0):
         raise SystemExit(REFUSALS['datadir_kd'])
     if args.i_video > 0 and args.N_iters // args.i_video > start // args.i_video:
         raise SystemExit(REFUSALS['i_video'].format(args.i_video))
+    refuse_negative_i_testset(args)
 
 
 def trainer_from_args(args, max_rays):
@@ -531,7 +461,7 @@ def eval_test_split(trainer, args, hwf, poses, gt):
 def train(args, log=print):
     """main.py without --render_only for --model_name nerf: returns the path of the last checkpoint"""
     from . import blender
-    from .frontend import load_checkpoint, mse2psnr
+    from .frontend import load_checkpoint
     from .teacher import get_rays
     start, ckpt = 0, None
     if args.pretrained_ckpt:
@@ -560,12 +490,8 @@ def train(args, log=print):
         f'{H} x {W}, focal {focal:.4f}; {args.N_rand} rays per step, {args.N_samples} + {args.N_importance} samples; {trainer.n_param} '
         f'parameters, {trainer.activation_bytes() / 2 ** 30:.2f} GiB of saved activations')
     crop = crop_bounds(H, W, args.precrop_frac)
-    hist_psnr = 0.
-    path = None
-    log('Begin training')
-    for i in range(start + 1, args.N_iters + 1):
-        t0 = time.time()
-        lr = learning_rate(i, args.lrate, args.lrate_decay, args.warmup_lr)
+
+    def draw(i):
         img_i = np.random.choice(i_train)                     # main.py:1213
         rays_o, rays_d = get_rays(H, W, focal, poses[img_i, :3, :4], device=dev)
         cropped = i < args.precrop_iters
@@ -573,36 +499,16 @@ def train(args, log=print):
             log(f'[Config] Center cropping of size {crop[1]} x {crop[3]} is enabled until iter {args.precrop_iters}')
         rows, cols = select_coords(H, W, args.N_rand, crop if cropped else None)
         rows, cols = torch.as_tensor(rows, device=dev), torch.as_tensor(cols, device=dev)
-        rays_o, rays_d = rays_o[rows, cols], rays_d[rows, cols]
-        target = images[img_i].to(dev)[rows, cols]
-        t_data = time.time() - t0
-        loss, loss_rgb = trainer.step(rays_o, rays_d, target, lr, perturb=args.perturb, raw_noise_std=args.raw_noise_std)
-        loss_v, rgb_v = float(loss.item()), float(loss_rgb.item())
-        t_batch = time.time() - t0
-        if not math.isfinite(loss_v):
-            raise R2LError(f'the loss is {loss_v} at iteration {i} (LR {lr:.10f})')
-        psnr = mse2psnr(rgb_v)
-        hist_psnr = psnr if i == start + 1 else hist_psnr * 0.95 + psnr * 0.05
-        if i % args.i_print == 0:
-            log(f'[TRAIN] Iter {i} data_time {t_data:.4f} batch_time {t_batch:.4f} loss {loss_v:.6f} psnr {psnr:.4f} hist_psnr {hist_psnr:.4f} '
-                f'LR {lr:.10f}')
-        if i % args.i_testset == 0:                           # main.py:1442-1471
-            log(f'Iter {i} Testing...')
-            t_ = time.time()
-            tp, tp2 = eval_test_split(trainer, args, (H, W, focal), poses[i_test], images[i_test])
-            if tp2 > best_psnr:
-                best_psnr, best_psnr_step = tp2, i
-                best = save_train_checkpoint(os.path.join(weights_dir, 'ckpt_best.tar'), trainer, i, best_psnr, best_psnr_step)
-                log(f'Iter {i} Save the best checkpoint: "{best}".')
-            log(f'[TEST] Iter {i} TestPSNR {tp:.4f} TestPSNRv2 {tp2:.4f} BestPSNRv2 {best_psnr:.4f} (Iter {best_psnr_step}) '
-                f'TrainHistPSNR {hist_psnr:.4f} LR {lr:.8f} Time {time.time() - t_:.1f}s')
-        if i % args.i_weights == 0:
-            path = save_train_checkpoint(os.path.join(weights_dir, 'ckpt.tar'), trainer, i, best_psnr, best_psnr_step)
-            log(f'Iter {i} Save checkpoint: "{path}".')
-    if args.N_iters > start and args.N_iters % args.i_weights != 0:
-        path = save_train_checkpoint(os.path.join(weights_dir, 'ckpt.tar'), trainer, args.N_iters, best_psnr, best_psnr_step)
-        log(f'Iter {args.N_iters} Save checkpoint: "{path}".')
-    return path
+        return rays_o[rows, cols], rays_d[rows, cols], images[img_i].to(dev)[rows, cols]
+
+    def test_pass(i):                         # no further [TEST] fields, no line after it
+        test_psnr, test_psnr_v2 = eval_test_split(trainer, args, (H, W, focal), poses[i_test], images[i_test])
+        return test_psnr, test_psnr_v2, '', None
+
+    # the [TRAIN] line's psnr is of img2mse(rgb) alone (main.py:1377-1379)
+    return run_iterations(args, trainer, start, (best_psnr, best_psnr_step), weights_dir, log, draw=draw,
+                          after_step=lambda batch, loss_rgb: float(loss_rgb.item()), test_pass=test_pass,
+                          step_args=dict(raw_noise_std=args.raw_noise_std))
 
 
 def main(argv=None):

@@ -126,14 +126,8 @@ def _fake_trainer(T, plan):
     """An R2LTrainer's state handling over host buffers (the constructor wants a device; the state-dict code does not)."""
     tr = object.__new__(T.R2LTrainer)
     tr.plan = plan
-    tr._slices, off = T.OrderedDict(), 0
-    for p in plan:
-        for kind, shape in (('weight', (p['out_dim'], p['in_dim'])), ('bias', (p['out_dim'],))):
-            cnt = int(np.prod(shape))
-            tr._slices[f"{p['key']}.{kind}"] = (off, cnt, shape)
-            off += cnt
-    tr.n_param, tr.t, tr.lr = off, 0, 0.
-    tr._param, tr._grad, tr._m, tr._v = (torch.zeros(off) for _ in range(4))
+    tr._set_layout([(p['key'], p['in_dim'], p['out_dim']) for p in plan])
+    tr._param, tr._grad, tr._m, tr._v = (torch.zeros(tr.n_param) for _ in range(4))
     tr.p, tr.g, tr.exp_avg, tr.exp_avg_sq = (tr._views(b) for b in (tr._param, tr._grad, tr._m, tr._v))
     return tr
 

@@ -104,6 +104,7 @@ def test_checkpoint_keys(pkg, tmp_path):
     (['--data_mode', 'rays'], '--data_mode rays: the teacher trains on images'),
     (['--model_name', 'R2L'], '--model_name R2L: train_teacher.py trains --model_name nerf'),
     (['--render_only'], 'train_teacher.py trains; render with main.py'),
+    (['--i_testset', '-5'], '--i_testset -5: a positive interval, or 0 for no test renders'),
 ])
 def test_each_refused_mode_exits_with_its_line(pkg, tmp_path, extra, line):
     from efficient_nerf_amd import train_teacher as TT

@@ -21,7 +21,7 @@ from efficient_nerf_amd import train_teacher as TT  # noqa: E402
 
 PEAK_TFLOPS = 157.3      # fp32 MFMA: 256 FLOP/clk/CU x 256 CUs x 2.4 GHz (csrc/r2l_generic.hip's header)
 STAGES = {'_linear': 'forward', '_grad_input': 'g_x', '_grad_weight': 'g_W', '_scan_forward': 'scans', '_scan_backward': 'scans',
-          '_relu_backward': 'element-wise', '_embed': 'element-wise', 'adam': 'element-wise'}
+          '_act_backward': 'element-wise', '_embed': 'element-wise', 'adam': 'element-wise'}
 
 
 def timed(fn, steps, warmup):

@@ -15,6 +15,7 @@ import torch  # noqa: E402
 import _pkg  # noqa: E402
 
 _pkg.load()
+from efficient_nerf_amd.generic import _act_code  # noqa: E402
 from efficient_nerf_amd.train import R2LTrainer, init_state_dict  # noqa: E402
 
 PEAK_TFLOPS = 157.3      # fp32 MFMA: 256 FLOP/clk/CU x 256 CUs x 2.4 GHz (csrc/r2l_generic.hip's header)
@@ -60,10 +61,11 @@ def main():
     parts = {
         'sample + embed': lambda: tr.embed(ro, rd, 1., t_rand),
         'forward': lambda: tr.forward(emb, n),
-        'g_x': lambda: [tr._grad_input(i, Z[:, :tr.plan[i]['out_dim']], Y[:, :tr.plan[i]['in_dim']], False) for i in range(1, len(tr.plan))],
-        'g_W': lambda: [tr._grad_weight(i, Z[:, :p['out_dim']], emb if i == 0 else acts[i - 1]) for i, p in enumerate(tr.plan)],
-        'element-wise': lambda: [tr._act_backward(i, R[:, :tr.plan[i]['out_dim']], acts[i], None, 1.0, Z[:, :tr.plan[i]['out_dim']],
-                                                  R[:, :tr.plan[i]['out_dim']] if tr.plan[i].get('block_out') else None, False, None)
+        'g_x': lambda: [tr._grad_input(p['key'], Z[:, :p['out_dim']], Y[:, :p['in_dim']], False) for p in tr.plan[1:]],
+        'g_W': lambda: [tr._grad_weight(p['key'], Z[:, :p['out_dim']], emb if i == 0 else acts[i - 1]) for i, p in enumerate(tr.plan)],
+        'element-wise': lambda: [tr._act_backward(tr.plan[i]['key'], R[:, :tr.plan[i]['out_dim']], acts[i], Z[:, :tr.plan[i]['out_dim']],
+                                                  _act_code(tr.plan[i]['act']),
+                                                  g_res=R[:, :tr.plan[i]['out_dim']] if tr.plan[i].get('block_out') else None)
                                  for i in [0] + list(body)],
         'Adam': lambda: tr.adam(0.0),
     }
