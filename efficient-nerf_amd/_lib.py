@@ -124,6 +124,7 @@ SIGNATURES = {
     'r2l_train_mse_loss': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, C.c_longlong, _vp]),
     'r2l_train_adam': (C.c_int, [_vp, _vp, _vp, _vp, C.c_longlong, C.c_double, C.c_longlong, _vp]),
     'r2l_train_jitter_z': (C.c_int, [_vp, _vp, C.c_int, C.c_int, _vp, _vp]),
+    'r2l_train_sum_parts': (C.c_int, [_vp, C.c_longlong, C.c_int, _f, C.c_longlong, _vp, _vp]),
     # real images to ray rows (csrc/r2l_convert.hip)
     'r2l_rays_from_images': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_double, C.c_int, _vp, C.c_longlong, _vp, _vp]),
     # rays for online distillation (csrc/r2l_online.hip)

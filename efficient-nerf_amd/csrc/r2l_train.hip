@@ -15,6 +15,7 @@
 //                            + the per-ray error the hard-ray pool sorts (main.py:1410-1413)
 //   r2l_train_adam           torch.optim.Adam's update (no weight decay, no amsgrad) over flat buffers, one launch
 //   r2l_train_jitter_z       main.py:684-699 / model/nerf_raybased.py:117-123: stratified jitter of the sample depths
+//   r2l_train_sum_parts      the ranks' gradients of a ray-sharded step, weighted and added in rank order (flat_trainer.py)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -290,6 +291,48 @@ __global__ void r2l_jitter_z_kernel(const float* __restrict__ z_vals, const floa
     z_out[gid] = __fadd_rn(lower, __fmul_rn(__fsub_rn(upper, lower), t_rand[gid]));
 }
 
+// out[i] = (...((w0 p0[i]) + w1 p1[i]) + ...) + w_{P-1} p_{P-1}[i]: every product and every sum rounded to fp32 on its own (the file
+// is built without contraction; the intrinsics say so again), in part order -- what torch's mul and add give, and what one process
+// gives that holds all the parts.  A streaming pass: 16-byte loads and stores over the first n_vec * 4 elements where the pointers
+// and the pitch allow them (n_vec = 0 otherwise), one element per thread behind them, grid-stride over both.  `out` may be part 0:
+// a thread has read every part's element(s) before it writes its own.
+#define SUM_MAX_PARTS 64
+#define SUM_BLOCK 256
+#define SUM_MAX_BLOCKS 2048
+struct r2l_sum_weights {
+    float w[SUM_MAX_PARTS];
+};
+
+__global__ __launch_bounds__(SUM_BLOCK) void r2l_sum_parts_kernel(const float* parts, long long pitch, int n_part, r2l_sum_weights wt,
+                                                                  long long count, long long n_vec, float* out) {
+    const long long n_item = n_vec + (count - 4 * n_vec);
+    const long long stride = (long long)gridDim.x * SUM_BLOCK;
+    for (long long it = (long long)blockIdx.x * SUM_BLOCK + threadIdx.x; it < n_item; it += stride) {
+        if (it < n_vec) {
+            const float4 p0 = *reinterpret_cast<const float4*>(parts + 4 * it);
+            float4 acc;
+            acc.x = __fmul_rn(p0.x, wt.w[0]);
+            acc.y = __fmul_rn(p0.y, wt.w[0]);
+            acc.z = __fmul_rn(p0.z, wt.w[0]);
+            acc.w = __fmul_rn(p0.w, wt.w[0]);
+            for (int k = 1; k < n_part; ++k) {
+                const float4 p = *reinterpret_cast<const float4*>(parts + k * pitch + 4 * it);
+                const float w = wt.w[k];
+                acc.x = __fadd_rn(acc.x, __fmul_rn(p.x, w));
+                acc.y = __fadd_rn(acc.y, __fmul_rn(p.y, w));
+                acc.z = __fadd_rn(acc.z, __fmul_rn(p.z, w));
+                acc.w = __fadd_rn(acc.w, __fmul_rn(p.w, w));
+            }
+            *reinterpret_cast<float4*>(out + 4 * it) = acc;
+        } else {
+            const long long i = 4 * n_vec + (it - n_vec);
+            float acc = __fmul_rn(parts[i], wt.w[0]);
+            for (int k = 1; k < n_part; ++k) acc = __fadd_rn(acc, __fmul_rn(parts[k * pitch + i], wt.w[k]));
+            out[i] = acc;
+        }
+    }
+}
+
 static int launch_status(const char* what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "%s launch: %s", what, hipGetErrorString(e));
@@ -417,6 +460,33 @@ int r2l_train_jitter_z(const float* z_vals_dev, const float* t_rand_dev, int n, 
     hipLaunchKernelGGL(r2l_jitter_z_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, z_vals_dev,
                        t_rand_dev, (long long)n, n_sample, z_out_dev);
     return launch_status("r2l_train_jitter_z");
+}
+
+int r2l_train_sum_parts(const float* parts_dev, long long pitch_floats, int n_part, const float* weights, long long count,
+                        float* out_dev, void* stream) {
+    if (n_part < 1 || n_part > SUM_MAX_PARTS || !weights || count < 0 || (count != 0 && (!parts_dev || !out_dev)) ||
+        (n_part > 1 && pitch_floats < count))
+        return r2l_set_error(R2L_EINVAL, "bad argument to r2l_train_sum_parts (n_part=%d, 1 .. %d; count=%lld pitch=%lld)", n_part,
+                             SUM_MAX_PARTS, count, pitch_floats);
+    // out may be part 0 exactly; any other overlap with the parts would be read after it was written
+    if (count > 0 && out_dev != parts_dev) {
+        const float* p_end = parts_dev + (size_t)(n_part - 1) * pitch_floats + count;
+        if (out_dev < p_end && parts_dev < out_dev + count)
+            return r2l_set_error(R2L_EINVAL, "r2l_train_sum_parts: out overlaps the parts (it may be part 0 itself, nothing else)");
+    }
+    int rc = r2l_require_gfx950(nullptr);
+    if (rc) return rc;
+    if (count == 0) return R2L_OK;
+    r2l_sum_weights wt;
+    for (int k = 0; k < SUM_MAX_PARTS; ++k) wt.w[k] = k < n_part ? weights[k] : 0.0f;
+    const bool aligned = (((uintptr_t)parts_dev | (uintptr_t)out_dev) & 15) == 0 && (n_part == 1 || pitch_floats % 4 == 0);
+    const long long n_vec = aligned ? count / 4 : 0;
+    const long long n_item = n_vec + (count - 4 * n_vec);
+    long long blocks = (n_item + SUM_BLOCK - 1) / SUM_BLOCK;
+    if (blocks > SUM_MAX_BLOCKS) blocks = SUM_MAX_BLOCKS;
+    hipLaunchKernelGGL(r2l_sum_parts_kernel, dim3((unsigned)blocks), dim3(SUM_BLOCK), 0, (hipStream_t)stream, parts_dev, pitch_floats,
+                       n_part, wt, count, n_vec, out_dev);
+    return launch_status("r2l_train_sum_parts");
 }
 
 }  // extern "C"

@@ -200,13 +200,59 @@ def all_gather_cat(t, group=None):
     world = dist.get_world_size(group)
     t = t.contiguous()
     out = torch.empty((world * t.shape[0],) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+    return all_gather_into(out, t, group)
+
+
+def all_gather_into(out, t, group=None):
+    """all_gather_cat into a kept contiguous buffer `out` of world * t.numel() elements (a training step's exchange allocates it once)"""
+    t = t.contiguous()
+    assert out.is_contiguous() and out.numel() == dist.get_world_size(group) * t.numel() and out.dtype == t.dtype and out.device == t.device
     if t.is_cuda and dist.get_backend(group) == 'gloo':
         host = torch.empty(out.shape, dtype=out.dtype)
-        dist.all_gather_into_tensor(host, t.cpu(), group=group)
+        dist.all_gather_into_tensor(host.view(-1), t.cpu().view(-1), group=group)
         out.copy_(host)
     else:
-        dist.all_gather_into_tensor(out, t, group=group)
+        dist.all_gather_into_tensor(out.view(-1), t.view(-1), group=group)
     return out
+
+
+def rank_world(group=None):
+    """(rank, world) of this process: (0, 1) without an initialised process group"""
+    if not dist.is_initialized():
+        return 0, 1
+    return dist.get_rank(group), dist.get_world_size(group)
+
+
+def shard_weights(n, world):
+    """([(r0, r1)] of every rank's contiguous slice of n rays, [n_r / n]): what a ray-sharded training step cuts and weighs by"""
+    bounds = [row_shard(n, r, world) for r in range(world)]
+    return bounds, [(b - a) / n if n else 0. for a, b in bounds]
+
+
+def seed_all(seed=None, group=None):
+    """Every rank seeds numpy's and torch's generators (host and device) with one seed: `seed`, or a draw from rank 0's numpy stream.
+    From then on the ranks' host and device draws are the same.  Returns the seed; does nothing (None) for one rank."""
+    import numpy as np
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return None
+    obj = [None]
+    if dist.get_rank(group) == 0:
+        obj = [int(seed) if seed is not None and int(seed) >= 0 else int(np.random.randint(0, 2 ** 31 - 1))]
+    dist.broadcast_object_list(obj, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
+    np.random.seed(obj[0])
+    torch.manual_seed(obj[0])
+    return obj[0]
+
+
+def any_rank(flag, device=None, group=None):
+    """True on every rank when `flag` holds on any: one MAX all-reduce of one int"""
+    if not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return bool(flag)
+    t = torch.tensor([1 if flag else 0], dtype=torch.int32)
+    if dist.get_backend(group) == 'nccl':
+        t = t.to(device)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX, group=group)
+    return bool(int(t.cpu()[0]))
 
 
 def agree_act_exponents(eng, group=None):

@@ -153,6 +153,64 @@ class FlatAdam:
             check(lib().r2l_train_adam(dptr(self._param), dptr(self._grad), dptr(self._m), dptr(self._v), self.n_param, float(lr), self.t,
                                        current_stream()))
 
+    # ---- a step whose rays are sharded over the ranks ------------------------------------------------------------------------
+    def exchange_gradients(self, group, n_local, n_total, loss=None, err=None):
+        """After forward_backward on this rank's slice dist.row_shard(n_total, rank, world) of a step's rays (n_local of them; an
+        empty slice runs no layer launch): ONE all-gather of every rank's [gradient | loss | per-ray error] row into a kept
+        [world, row] buffer, then r2l_train_sum_parts over the gradient columns into the flat gradient buffer, parts in rank order
+        with the weights n_r / n_total (every rank's loss kernel divided by its own 3 n_r) -- a fixed-order sum, not an all-reduce:
+        the same bits on every rank, under either backend, from run to run, and what one process computes that holds all the
+        parts.  adam() then runs as on one rank.  An empty slice contributes exact zeros, whatever its buffers held.
+        loss [1] / err [>= n_local]: this rank's (default: the trainer's own buffers).
+        Returns (the step's loss [1] = sum of w_r loss_r in rank order, written to `loss`; the per-ray error [n_total] in ray order)."""
+        import ctypes as C
+        import torch.distributed as td
+        from . import dist as D
+        self._need_state()
+        world, rank = td.get_world_size(group), td.get_rank(group)
+        loss = self._loss if loss is None else loss
+        err = self._err if err is None else err
+        bounds, weights = D.shard_weights(n_total, world)
+        counts = [b - a for a, b in bounds]
+        if n_total < 1 or n_local != counts[rank] or max(counts) > self.max_rays:
+            raise R2LError(f'rank {rank} of {world} holds {n_local} of a step\'s {n_total} rays, its slice is {counts[rank]} (max_rays = {self.max_rays})')
+        P = self.n_param
+        row = (P + 1 + self.max_rays + 3) // 4 * 4          # rows stay 16-byte aligned in the gathered buffer
+        if getattr(self, '_xall', None) is None or tuple(self._xall.shape) != (world, row):
+            self._xsend = torch.zeros((row,), dtype=torch.float32, device=self.device)
+            self._xall = torch.empty((world, row), dtype=torch.float32, device=self.device)
+        send = self._xsend
+        with torch.cuda.device(self.device):
+            if n_local == 0:
+                send.zero_()
+            else:
+                send[:P].copy_(self._grad)
+                send[P:P + 1].copy_(loss)
+                send[P + 1:P + 1 + n_local].copy_(err[:n_local])
+            D.all_gather_into(self._xall, send, group)
+            w = (C.c_float * world)(*weights)
+            flat = self._xall.view(-1)
+            check(lib().r2l_train_sum_parts(dptr(flat), row, world, w, P, dptr(self._grad), current_stream()))
+            check(lib().r2l_train_sum_parts(dptr(flat[P:]), row, world, w, 1, dptr(loss), current_stream()))
+            err_all = torch.cat([self._xall[r, P + 1:P + 1 + c] for r, c in enumerate(counts)])
+        return loss, err_all
+
+    def check_agreement(self, group, what=''):
+        """The ranks of a ray-sharded run must hold the same parameters bit for bit: two 64-bit checksums of the parameter buffer's
+        words (their sum, and their sum weighted by position) are all-gathered and compared for equality.  Every rank raises when
+        any two differ."""
+        import torch.distributed as td
+        from . import dist as D
+        self._need_state()
+        bits = torch.cat([self._param, self._m, self._v]).view(torch.int32).to(torch.int64)
+        pos = torch.arange(1, bits.numel() + 1, dtype=torch.int64, device=bits.device)
+        mine = torch.stack([bits.sum(), (bits * pos).sum()])
+        got = D.all_gather_cat(mine[None], group).cpu()
+        if not bool((got == got[0]).all()):
+            bad = [r for r in range(got.shape[0]) if not bool((got[r] == got[0]).all())]
+            raise R2LError(f'the ranks\' weights have diverged{what}: rank(s) {bad} of {td.get_world_size(group)} hold other parameters or Adam '
+                           f'moments than rank 0 (checksums {[tuple(int(v) for v in g) for g in got]}); nothing is written from them')
+
     # ---- the optimizer's state ---------------------------------------------------------------------------------------------
     def optimizer_state_dict(self):
         """torch.optim.Adam.state_dict(): parameters indexed in model.parameters() order (weight then bias, layer by layer)."""

@@ -108,6 +108,8 @@ FLAGS = [
     ('--watch_every', dict(type=int, default=8)),
     # N > 1 without torchrun: main.py / create_data.py start the N ranks themselves before importing torch (launch.py)
     ('--gpus', dict(type=int, default=0)), ('--launch_timeout', dict(type=float, default=0.)),
+    # training on several ranks: the seed every rank gives numpy's and torch's generators at start-up (-1: a draw from rank 0's stream)
+    ('--dist_seed', dict(type=int, default=-1)),
 ]
 
 
@@ -776,8 +778,14 @@ def main(argv=None):
             raise SystemExit('without --render_only main.py trains the student, which is built for ray shards: pass --data_mode rays '
                              '--datadir_kd DIR (or --render_only --pretrained_ckpt X.tar to render)')
         from . import train as T
-        torch.cuda.set_device(D.local_device(0))
+        rank, local_rank, world = D.init()
+        torch.cuda.set_device(D.local_device(local_rank))
+        D.seed_all(args.dist_seed)            # several ranks: the same host and device draws on all of them; one rank seeds nothing
         T.train(args, log=lambda *a, **k: print(*a, **k, flush=True))
+        if world > 1:                         # every rank is through its last collective
+            import torch.distributed as tdist
+            D.barrier_sync()
+            tdist.destroy_process_group()
         return 0
     if not args.pretrained_ckpt:
         raise SystemExit('--pretrained_ckpt is required with --render_only')

@@ -66,26 +66,60 @@ class OnlineTeacherSource:
                                       current_stream()))
         return ro, rd
 
-    def batch(self, step, n):
-        """(rays_o, rays_d, target), each [n, 3] float32 on the engine's device"""
+    def batch(self, step, n, rows=None, group=None):
+        """(rays_o, rays_d, target), each [n, 3] float32 on the engine's device.  rows = (r0, r1) on a rank of a ray-sharded run
+        (torch.distributed group `group`): every rank draws the poses and launches the rays of all n, renders the targets of its
+        rows only, and the targets are all-gathered (the hard-ray pool needs every row); on a watched step a rank checks its own
+        rows, a miss on any rank (one MAX all-reduce) moves every rank's engine one rung down, and all render again."""
         step, n = int(step), int(n)
         poses, focals = self.draws(step)
         ro, rd = self._rays_fn(poses, torch.from_numpy(focals).to(torch.float32), step, n)       # get_rays rounds the focal the same way
         eng = self.engine
-        out = eng.render_rays(ro, rd)
+        if rows is None:
+            lro, lrd, any_rank = ro, rd, bool
+        else:
+            from . import dist as D
+            r0, r1 = rows
+            lro, lrd = ro[r0:r1].contiguous(), rd[r0:r1].contiguous()
+            any_rank = lambda flag: D.any_rank(flag, self.device, group)
+
+        def render():
+            if lro.shape[0] == 0:
+                return {'rgb_map': torch.empty((0, 3), dtype=torch.float32, device=ro.device)}
+            return eng.render_rays(lro, lrd)
+
+        out = render()
         if self.watch_every and step % self.watch_every == 0 and hasattr(eng, 'spot_check'):
             for _ in range(len(getattr(eng, 'LADDER', (0,)))):
-                ok, d = eng.spot_check(ro, rd, out)
+                ok, d = eng.spot_check(lro, lrd, out) if lro.shape[0] else (True, {})
                 self.checks += 1
-                if ok:
+                if not any_rank(not ok):
                     break
                 was = getattr(eng, 'precision_name', '?')
                 now = eng.step_down()
                 self.fallbacks.append({'step': step, 'from': was, 'to': now, 'diffs': d})
-                out = eng.render_rays(ro, rd)
-                self.log(f'[precision] step {step}: {was} is {d} from fp16x3 on {getattr(eng, "WATCH_RAYS", "a sample")} of the batch\'s rays -> {now}; '
-                         f'batch rendered again')
-        return ro, rd, out['rgb_map']
+                out = render()
+                what = d if not ok else 'off on the rows of another rank,'
+                log = self.log if rows is None or D.rank_world(group)[0] == 0 else (lambda *a, **k: None)       # one line per run, not per rank
+                log(f'[precision] step {step}: {was} is {what} from fp16x3 on {getattr(eng, "WATCH_RAYS", "a sample")} of the batch\'s rays '
+                    f'-> {now}; batch rendered again')
+        target = out['rgb_map']
+        if rows is not None:
+            import torch.distributed as td
+            target = D.gather_rows(target[None].contiguous(), n, 1, td.get_world_size(group), group)[0]
+        return ro, rd, target
+
+
+def agree_teacher_precision(eng, group=None):
+    """`--precision auto` measures the teacher's mode at start-up on every rank; the ranks render rows of the same batches, so rank 0's
+    (fine, coarse) pair is broadcast and adopted.  No-op for one rank and for engines without modes (the generic fp32 path)."""
+    import torch.distributed as td
+    if not td.is_initialized() or td.get_world_size(group) == 1 or not hasattr(eng, 'set_precision_pair'):
+        return
+    obj = [(int(eng.precision), int(eng.precision_coarse))]
+    td.broadcast_object_list(obj, src=td.get_global_rank(group, 0) if group is not None else 0, group=group)
+    if obj[0] != (int(eng.precision), int(eng.precision_coarse)):
+        eng.set_precision_pair(obj[0][1], obj[0][0])
 
 
 def check_online_args(args):

@@ -255,6 +255,41 @@ class R2LTrainer(FlatAdam):
         return self.render_rays(ro.view(-1, 3), rd.view(-1, 3), out=out)
 
 
+class ShardedStep:
+    """A trainer's step on the ranks of one torch.distributed group: the loop is replicated, the rays are sharded.  Every rank hands
+    step() the same full batch; it draws t_rand for all n rays (the draw one rank makes), runs forward_backward on its slice
+    dist.row_shard(n, rank, world), exchanges (FlatAdam.exchange_gradients: the ranks' gradients added in rank order) and runs Adam: the
+    same update of the same bits on every rank.  Returns (loss [1], err [n]) of the whole batch, as R2LTrainer.step does.  Everything
+    else (state_dict, render, checkpoint_networks, ...) is the trainer's own."""
+
+    def __init__(self, trainer, group=None):
+        import torch.distributed as td
+        self.trainer, self.group = trainer, group
+        self.rank, self.world = td.get_rank(group), td.get_world_size(group)
+
+    def __getattr__(self, name):
+        return getattr(self.__dict__['trainer'], name)
+
+    def step(self, rays_o, rays_d, target, lr, perturb=1., t_rand=None):
+        from .dist import row_shard
+        tr = self.trainer
+        n = rays_o.shape[0]
+        r0, r1 = row_shard(n, self.rank, self.world)
+        if perturb > 0. and t_rand is None:
+            with torch.cuda.device(tr.device):
+                t_rand = torch.rand((n, tr.n_sample), dtype=torch.float32, device=tr.device)       # jitter_z_vals' draw for n rays
+        if r1 > r0:
+            tr.forward_backward(rays_o[r0:r1], rays_d[r0:r1], target[r0:r1], perturb, None if t_rand is None else t_rand[r0:r1])
+        loss, err = tr.exchange_gradients(self.group, r1 - r0, n)
+        tr.adam(lr)
+        return loss, err
+
+
+def refuse_more_ranks_than_rays(world, n_rays):
+    if world > n_rays:
+        raise SystemExit(f'{world} ranks for steps of {n_rays} rays: a rank without rays has nothing to do; lower --gpus or raise --N_rand')
+
+
 # ---------------------------------------------------------------------------------------------------------------------------
 # the loop of main.py:1136-1513
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -361,7 +396,7 @@ def refuse_negative_i_testset(args):
 
 
 def run_iterations(args, trainer, start, best, weights_dir, log, *, draw, after_step, test_pass=None,
-                   ckpt_name=lambda it: 'ckpt.tar', step_args={}):
+                   ckpt_name=lambda it: 'ckpt.tar', step_args={}, writer=True, guard=None):
     """Iterations start + 1 .. N_iters of main.py:1136-1513 on either trainer: the learning rate, the step, the [TRAIN] line, the
     test renders every --i_testset iterations (0: none) with the best checkpoint and the [TEST] line, the periodic and the final
     checkpoint.  Returns the path of the last checkpoint written.  What differs between the trainers comes in as
@@ -369,10 +404,20 @@ def run_iterations(args, trainer, start, best, weights_dir, log, *, draw, after_
       after_step(batch, second) -> the mse the line's psnr is of, or None for the loss; second: what trainer.step returned second
       test_pass(i)              -> (test_psnr, test_psnr_v2, further fields of the [TEST] line, a line to log after it or None)
       ckpt_name(i)              -> the periodic checkpoint's file name
-    best: (best_psnr, best_psnr_step) so far; step_args: passed on to trainer.step beside perturb."""
+    best: (best_psnr, best_psnr_step) so far; step_args: passed on to trainer.step beside perturb.
+    On the ranks of a ray-sharded run every rank runs this loop on the same batches: writer is True on the one rank that renders the
+    test split and writes files (the others go on to the next step's collective), and guard(i) is entered by every rank before
+    anything is written at iteration i (it raises on every rank when their weights differ); test_pass is then given on every rank
+    or on none."""
     from .frontend import mse2psnr
     best_psnr, best_psnr_step = best
     save = lambda name, it: save_train_checkpoint(os.path.join(weights_dir, name), trainer, it, best_psnr, best_psnr_step)
+    guarded = [None]
+
+    def agree(it):
+        if guard is not None and guarded[0] != it:
+            guard(it)
+            guarded[0] = it
     hist_psnr = 0.
     path = None
     log('Begin training')
@@ -392,7 +437,10 @@ def run_iterations(args, trainer, start, best, weights_dir, log, *, draw, after_
         if i % args.i_print == 0:
             log(f'[TRAIN] Iter {i} data_time {t_data:.4f} batch_time {t_batch:.4f} loss {loss_v:.6f} psnr {psnr:.4f} hist_psnr {hist_psnr:.4f} '
                 f'LR {lr:.10f}')
-        if test_pass is not None and args.i_testset and i % args.i_testset == 0:      # main.py:1442-1471
+        testing = test_pass is not None and args.i_testset and i % args.i_testset == 0
+        if testing:
+            agree(i)
+        if testing and writer:                                                          # main.py:1442-1471
             log(f'Iter {i} Testing...')
             t_ = time.time()
             test_psnr, test_psnr_v2, fields, after = test_pass(i)
@@ -406,11 +454,15 @@ def run_iterations(args, trainer, start, best, weights_dir, log, *, draw, after_
             if after:
                 log(after)
         if i % args.i_weights == 0:
-            path = save(ckpt_name(i), i)
-            log(f'Iter {i} Save checkpoint: "{path}".')
-    if args.N_iters > start and args.N_iters % args.i_weights != 0:
-        path = save(ckpt_name(args.N_iters), args.N_iters)
-        log(f'Iter {args.N_iters} Save checkpoint: "{path}".')
+            agree(i)
+            if writer:
+                path = save(ckpt_name(i), i)
+                log(f'Iter {i} Save checkpoint: "{path}".')
+    if args.N_iters > start:
+        agree(args.N_iters)
+        if writer and args.N_iters % args.i_weights != 0:
+            path = save(ckpt_name(args.N_iters), args.N_iters)
+            log(f'Iter {args.N_iters} Save checkpoint: "{path}".')
     return path
 
 
@@ -496,7 +548,11 @@ def _train(args, log, engines):
     """main.py without --render_only for --model_name R2L / nerf_v3.2, --data_mode rays; with --kd_online the rays of every step are
     rendered by the teacher on the device (online.py) instead of read from shards, and everything behind them is the same code."""
     from .create_data import BlenderDataset_v2
+    from .dist import rank_world, row_shard
     from .frontend import load_checkpoint
+    rank, world = rank_world()       # several ranks: the loop is replicated, the rays of a step are sharded (ShardedStep)
+    if rank != 0:
+        log = lambda *a, **k: None
     online = bool(getattr(args, 'kd_online', False))
     if online:                 # every step's rays from the teacher (online.py) instead of shards
         from .online import check_online_args, source_from_args
@@ -516,13 +572,27 @@ def _train(args, log, engines):
     pool = HardRayPool(args.hard_ratio, args.hard_mul) if parse_hard_ratio(args.hard_ratio) else None
     n_hard_out = pool.counts(batch_size)[1] if pool else 0
     refuse_negative_i_testset(args)
-    trainer = trainer_from_args(args, batch_size + n_hard_out)
+    refuse_more_ranks_than_rays(world, batch_size)
+    max_rays = -(-(batch_size + n_hard_out) // world)         # a rank's slice of the step's rays and of the pool's share
+    trainer = trainer_from_args(args, max_rays)
     dev = trainer.device
     if online:
         source, source_desc = source_from_args(args, log=log)
         engines.append(source.engine)
-    test, missing = load_test_split(args, device=dev)        # the ground truth goes to the device once
-    if args.test_pretrained and (test is None or not args.pretrained_ckpt):
+        if world > 1:
+            from .online import agree_teacher_precision
+            agree_teacher_precision(source.engine)
+    if rank == 0:
+        test, missing = load_test_split(args, device=dev)        # the ground truth goes to the device once
+    else:
+        test, missing = None, 'rank 0 renders the test split'
+    has_test = test is not None
+    if world > 1:                # the other ranks enter the agreement guard where rank 0 renders
+        import torch.distributed as td
+        flag = [has_test]
+        td.broadcast_object_list(flag, src=0)
+        has_test = flag[0]
+    if rank == 0 and args.test_pretrained and (test is None or not args.pretrained_ckpt):
         raise SystemExit('--test_pretrained needs --pretrained_ckpt and a test split: ' +
                          (f'{missing} is not there' if test is None else 'no --pretrained_ckpt was given'))
     start = 0
@@ -543,13 +613,14 @@ def _train(args, log, engines):
     os.makedirs(weights_dir, exist_ok=True)
     log((f'Online distillation: {source_desc}; {batch_size} rays per step + {n_hard_out} hard rays; ' if online else
          f'Found {len(dataset)} shard(s) of {split} rays under "{datadir_kd}"; {args.N_rand} per step + {n_hard_out} hard rays; ') +
-        f'{trainer.n_param} parameters in {len(trainer.plan)} layers, {trainer.activation_bytes() / 2 ** 30:.2f} GiB of saved activations')
+        f'{trainer.n_param} parameters in {len(trainer.plan)} layers, {trainer.activation_bytes() / 2 ** 30:.2f} GiB of saved activations' +
+        (f'; {world} ranks, ≤ {max_rays} rays each' if world > 1 else ''))
     if test is None:
         log(f'No test renders during this run: {missing} is not there.')
     else:
         log(f'Test split: {len(test[0])} view(s) {test[1][0]} x {test[1][1]} from "{args.datadir}", ' +
             (f'rendered every {args.i_testset} iterations' if args.i_testset else 'not rendered while training (--i_testset 0)'))
-    if args.test_pretrained:                                  # main.py:1035-1047
+    if args.test_pretrained and rank == 0:                    # main.py:1035-1047
         log('Testing pretrained...')
         _, misc = eval_test_split(trainer, test)
         log(f"Pretrained test: TestPSNR {misc['test_psnr']:.4f} TestPSNRv2 {misc['test_psnr_v2']:.4f}")
@@ -557,7 +628,7 @@ def _train(args, log, engines):
 
     def draw(i):
         if online:
-            rays_o, rays_d, target = source.batch(i, batch_size)
+            rays_o, rays_d, target = source.batch(i, batch_size, rows=row_shard(batch_size, rank, world) if world > 1 else None)
         else:
             items = [dataset[int(next(order))] for _ in range(args.N_rand)]
             rays_o, rays_d, target = (torch.cat([it[k] for it in items], 0).to(dev) for k in range(3))
@@ -578,6 +649,11 @@ def _train(args, log, engines):
         _, misc = eval_test_split(trainer, test, savedir=testsavedir)
         return misc['test_psnr'], misc['test_psnr_v2'], f"TestSSIM {misc['test_ssim']:.4f} ", f'Saved rendered test images: "{testsavedir}"'
 
-    return run_iterations(args, trainer, start, (best_psnr, best_psnr_step), weights_dir, log, draw=draw, after_step=after_step,
-                          test_pass=test_pass if test is not None else None,
-                          ckpt_name=lambda it: f'ckpt_{it}.tar' if args.save_intermediate_models else 'ckpt.tar')       # main.py:1510
+    stepper, guard = trainer, None
+    if world > 1:
+        stepper = ShardedStep(trainer)
+        guard = lambda it: trainer.check_agreement(None, f' by iteration {it}')
+    return run_iterations(args, stepper, start, (best_psnr, best_psnr_step), weights_dir, log, draw=draw, after_step=after_step,
+                          test_pass=test_pass if has_test else None,
+                          ckpt_name=lambda it: f'ckpt_{it}.tar' if args.save_intermediate_models else 'ckpt.tar',      # main.py:1510
+                          writer=rank == 0, guard=guard)

@@ -500,6 +500,12 @@ int r2l_train_adam(float* param_dev, const float* grad_dev, float* exp_avg_dev, 
 /* PointSampler.sample_train with perturb > 0 (model/nerf_raybased.py:117-123): z_out [n, n_sample] = lower + (upper - lower) *
  * t_rand over the strata of z_vals_dev [n_sample]; feeds r2l_sample_points with z_per_ray = 1 */
 int r2l_train_jitter_z(const float* z_vals_dev, const float* t_rand_dev, int n, int n_sample, float* z_out_dev, void* stream);
+/* The ordered sum of the ranks' gradients of a ray-sharded step: out_dev[i] = (...((w0 p0[i]) + w1 p1[i]) + ...) + w_{P-1} p_{P-1}[i]
+ * for i < count, part k at parts_dev + k * pitch_floats.  Every product and every sum is rounded to fp32 on its own (no fused
+ * multiply-add) in part order: the bits of torch's separate mul and add, whatever the launch shape.  weights: n_part floats on the
+ * HOST, passed to the kernel by value; 1 <= n_part <= 64.  out_dev may be part 0 itself (no other overlap); count >= 0. */
+int r2l_train_sum_parts(const float* parts_dev, long long pitch_floats, int n_part, const float* weights, long long count,
+                        float* out_dev, void* stream);
 
 /* ---- real images to ray rows (csrc/r2l_convert.hip; host mirror: efficient-nerf_amd/convert_data.py) ----
  * utils/convert_original_data_to_rays_blender.py:142-223 as one gather: out_dev [rows, 9] = (rays_o, rays_d, rgb) of the pixels
