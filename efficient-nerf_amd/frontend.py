@@ -86,6 +86,8 @@ FLAGS = [
     ('--no_rand_focal', dict(action=_BOOL)),
     # ckpt_<i>.tar instead of ckpt.tar every --i_weights iterations (main.py:1510); the test split once from --pretrained_ckpt (main.py:1035)
     ('--save_intermediate_models', dict(action=_BOOL)), ('--test_pretrained', dict(action=_BOOL)),
+    # TestFLIP (main.py:371-379, :1468) behind TestSSIM on the [TEST] lines: metrics.flip of the rescaled stacks, on the library's kernels
+    ('--test_flip', dict(action=_BOOL)),
     # teacher training (train_teacher.py; names and defaults of option.py).  --no_batching, --precrop_iters and --precrop_frac above are
     # read by its loop
     ('--i_testset', dict(type=int, default=2000)), ('--i_video', dict(type=int, default=10000)),
@@ -330,6 +332,13 @@ def frame_errors(rgb, gt):
     return torch.mean((rgb - gt) ** 2), ssim_hwc(rgb, gt)
 
 
+def stack_flip(rgbs, gt):
+    """The report's TestFLIP (main.py:359-379, :393): FLIP of the two stacks [N, H, W, 3], each mapped to [-1, 1] by its own
+    minimum and maximum first, because the reference hands compute_flip what it rescaled for LPIPS"""
+    from .metrics import flip
+    return flip(rgbs.float(), gt.float(), rescale=True)
+
+
 def test_metrics(rgbs, gt, frame_mse, frame_ssim):
     """The test report's three numbers (main.py:384-391): test_psnr from the mean error over all frames, test_psnr_v2 the mean
     of the frames' PSNRs, test_ssim the mean of the frames' SSIMs.  rgbs, gt [N, H, W, 3] on one device; frame_mse / frame_ssim:
@@ -543,7 +552,7 @@ class _ImageWriter:
 
 
 def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=print, given_rays=None, frames_per_batch=None,
-                stats=None, watch_every=8):
+                stats=None, watch_every=8, test_flip=False):
     """main.py:189-398 for the R2L and nerf branches: render, per-frame timing lines, PSNR / SSIM when GT is given.
 
     The loop is the one bench.py times ("batch >= 8 frames per collective"): frames go in batches of
@@ -761,6 +770,8 @@ def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=pr
     misc = {}
     if gt_imgs is not None:
         misc.update(test_metrics(rgbs, gt_imgs.to(rgbs.device), mse_dev, ssim_dev))
+        if test_flip and rank == 0:     # on the gathered frames, all at once: main.py:359-379 rescales the whole stacks
+            misc['test_flip'] = stack_flip(rgbs, gt_imgs.to(rgbs.device))
     return rgbs, misc
 
 
@@ -838,7 +849,7 @@ def main(argv=None):
     st = {}
     with torch.no_grad():
         rgbs, misc = render_path(poses, hwf, kind, eng, gt_imgs=gt, savedir=outdir, log=log, given_rays=given, stats=st,
-                                 frames_per_batch=args.frames_per_batch or None, watch_every=args.watch_every)
+                                 frames_per_batch=args.frames_per_batch or None, watch_every=args.watch_every, test_flip=args.test_flip)
     dt = time.time() - t_
     if rank == 0:
         np.save(os.path.join(outdir, 'rgbs.npy'), st['host_frames'].numpy() if 'host_frames' in st else rgbs.cpu().numpy())
@@ -860,6 +871,6 @@ def main(argv=None):
                 f"{ {k: float('%.2e' % v) for k, v in w_['worst'].items()} }, {len(w_['fallbacks'])} fallback(s); mode at the end: {w_['precision']}")
         if 'test_psnr' in misc:
             log(f"[TEST] TestPSNR {misc['test_psnr']:.4f} TestPSNRv2 {misc['test_psnr_v2']:.4f} "
-                f"TestSSIM {misc['test_ssim']:.4f}")
+                f"TestSSIM {misc['test_ssim']:.4f}" + (f" TestFLIP {misc['test_flip']:.4f}" if 'test_flip' in misc else ''))
         log(f'Save renders: "{outdir}"')
     return 0

@@ -528,6 +528,27 @@ int r2l_rays_from_images(const unsigned char* images_dev, int n_img, int H0, int
 int r2l_rand_rays(const float* poses_dev, const float* focal_dev, int n_pose, int H, int W, unsigned long long seed, long long step,
                   long long n, float* rays_o_dev, float* rays_d_dev, long long* pixel_dev, void* stream);
 
+/* ---- FLIP of image pairs (csrc/r2l_flip.hip; host side: efficient-nerf_amd/metrics.py flip, flip_taps.py) ----
+ * FLIP.compute_flip(a, b, pixels_per_degree) of utils/flip_loss.py:70-130, the TestFLIP of the reference's [TEST] lines, on
+ * v = mul * (x - lo) + add of each image (three roundings, applied first; (0, 1, 0) is the identity, exactly): sRGB clamped to
+ * [0, 1] -> linear RGB -> XYZ -> YCxCz, the three contrast-sensitivity filters with replicate padding, linear RGB clamped to the unit
+ * box -> L*a*b* -> Hunt -> HyAB -> redistribution (q_c 0.7, p_c 0.4, p_t 0.95), edge and point detection on (Y + 16) / 116
+ * (w 0.082, q_f 0.5, clamped to [0, 1]), result dE_c ^ (1 - dE_f).  Symmetric in its two images.  a_dev, b_dev: float32
+ * [n_img, H, W, 3]; map_dev [n_img, H, W] or NULL; frame_mean_dev [n_img]: each frame's mean.  The filter radii follow from
+ * pixels_per_degree as the reference derives them (10 and 9 at its default 67.02) and the taps are built on the host in float64;
+ * every filter runs as two 1-D passes.  Radii up to 16 (pixels_per_degree <= 118.4), H and W up to 32768: R2L_EINVAL beyond.
+ * workspace_dev: r2l_flip_workspace_floats(H, W, pixels_per_degree) floats (or a negative code), whatever n_img: the frames go
+ * through it one after another.  Plain stores and fixed-order sums, no atomics: the same inputs give the same bits, and the means
+ * are the same with and without a map.  n_img = 0 is a no-op. */
+long long r2l_flip_workspace_floats(int H, int W, double pixels_per_degree);
+int r2l_flip(const float* a_dev, const float* b_dev, int n_img, int H, int W, float a_lo, float a_mul, float a_add, float b_lo, float b_mul,
+             float b_add, double pixels_per_degree, float* map_dev, float* frame_mean_dev, float* workspace_dev, long long workspace_floats,
+             void* stream);
+/* The 1-D taps r2l_flip filters with, for tests and tools (host only, no device): taps_host [7][33] float32, rows A, RG, BY1, BY2
+ * (A = n (x) n, RG likewise, BY = t1 (x) t1 + t2 (x) t2; 2 radius_csf + 1 taps each, zeros behind) and G, D, P (edge = D (x) G,
+ * point = P (x) G, first factor along x; 2 radius_feature + 1 taps). */
+int r2l_flip_taps(double pixels_per_degree, float* taps_host, int* radius_csf, int* radius_feature);
+
 /* ---- training of the NeRF teacher (csrc/nerf_train.hip; host mirror: efficient-nerf_amd/train_teacher.py) ----
  * A teacher step is the launches above (layers, embedding, scans, loss, Adam) plus the backward pass of nerf_raw2outputs[_noise]:
  * g_raw_dev [n,S,4] from g_rgb_map_dev [n,3], the only output the losses reach (main.py:728 detaches z_samples).  raw [n,S,4],
