@@ -14,4 +14,4 @@ from ._lib import lib, R2LError, PREC_FP16X3, PREC_FP16X1, PREC_FP16_FP8, PREC_F
 from .r2l import PointSampler, PositionalEmbedder, R2LEngine, NeRF_v3_2, render_func, PREC_NAMES  # noqa: F401
 from .teacher import NeRFEngine, get_rays, ndc_rays, raw2outputs, sample_pdf, merge_sorted, render  # noqa: F401
 from .train import R2LTrainer, HardRayPool, learning_rate  # noqa: F401
-from .metrics import flip  # noqa: F401
+from .metrics import flip, LPIPS, load_lpips_weights  # noqa: F401

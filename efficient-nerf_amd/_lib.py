@@ -134,6 +134,12 @@ SIGNATURES = {
     'r2l_flip': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_double,
                            _vp, _vp, _vp, C.c_longlong, _vp]),
     'r2l_flip_taps': (C.c_int, [C.c_double, _vp, _vp, _vp]),
+    # LPIPS (csrc/r2l_lpips.hip)
+    'r2l_lpips_create': (C.c_int, [_vp, _vp, C.c_int]),
+    'r2l_lpips_destroy': (None, [_vp]),
+    'r2l_lpips_workspace_floats': (C.c_longlong, [C.c_int, C.c_int]),
+    'r2l_lpips': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                            _vp, _vp, _vp, C.c_longlong, _vp]),
     # teacher training (csrc/nerf_train.hip)
     'nerf_train_raw2outputs_backward': (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
 }

@@ -88,6 +88,9 @@ FLAGS = [
     ('--save_intermediate_models', dict(action=_BOOL)), ('--test_pretrained', dict(action=_BOOL)),
     # TestFLIP (main.py:371-379, :1468) behind TestSSIM on the [TEST] lines: metrics.flip of the rescaled stacks, on the library's kernels
     ('--test_flip', dict(action=_BOOL)),
+    # TestLPIPS (main.py:359-369, :1468) between TestSSIM and TestFLIP: metrics.LPIPS of the rescaled stacks, on the library's kernels, from
+    # the pretrained weights --lpips_weights points at (PATH, or PATH_A:PATH_B: metrics.load_lpips_weights); the AlexNet trunk only
+    ('--test_lpips', dict(action=_BOOL)), ('--lpips_weights', dict(type=str, default='')), ('--lpips_net', dict(type=str, default='alex')),
     # teacher training (train_teacher.py; names and defaults of option.py).  --no_batching, --precrop_iters and --precrop_frac above are
     # read by its loop
     ('--i_testset', dict(type=int, default=2000)), ('--i_video', dict(type=int, default=10000)),
@@ -339,6 +342,12 @@ def stack_flip(rgbs, gt):
     return flip(rgbs.float(), gt.float(), rescale=True)
 
 
+def stack_lpips(metric, rgbs, gt):
+    """The report's TestLPIPS (main.py:359-369, :392): metric, a metrics.LPIPS, of the two stacks [N, H, W, 3], each mapped to [-1, 1] by
+    its own minimum and maximum first"""
+    return metric(rgbs.float(), gt.float(), rescale=True)
+
+
 def test_metrics(rgbs, gt, frame_mse, frame_ssim):
     """The test report's three numbers (main.py:384-391): test_psnr from the mean error over all frames, test_psnr_v2 the mean
     of the frames' PSNRs, test_ssim the mean of the frames' SSIMs.  rgbs, gt [N, H, W, 3] on one device; frame_mse / frame_ssim:
@@ -552,7 +561,7 @@ class _ImageWriter:
 
 
 def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=print, given_rays=None, frames_per_batch=None,
-                stats=None, watch_every=8, test_flip=False):
+                stats=None, watch_every=8, test_flip=False, lpips=None):
     """main.py:189-398 for the R2L and nerf branches: render, per-frame timing lines, PSNR / SSIM when GT is given.
 
     The loop is the one bench.py times ("batch >= 8 frames per collective"): frames go in batches of
@@ -770,6 +779,8 @@ def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=pr
     misc = {}
     if gt_imgs is not None:
         misc.update(test_metrics(rgbs, gt_imgs.to(rgbs.device), mse_dev, ssim_dev))
+        if lpips is not None and rank == 0:
+            misc['test_lpips'] = stack_lpips(lpips, rgbs, gt_imgs.to(rgbs.device))
         if test_flip and rank == 0:     # on the gathered frames, all at once: main.py:359-379 rescales the whole stacks
             misc['test_flip'] = stack_flip(rgbs, gt_imgs.to(rgbs.device))
     return rgbs, misc
@@ -778,6 +789,8 @@ def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=pr
 def main(argv=None):
     from . import dist as D
     args = parse_args(argv)
+    from .metrics import LPIPS, lpips_weights_from_args
+    args.lpips_tensors = lpips_weights_from_args(args)        # --test_lpips: refused here, before a device is touched, or loaded once
     if not args.render_only:
         if args.model_name not in ('R2L', 'nerf_v3.2'):
             raise SystemExit(f'--model_name {args.model_name} without --render_only: teacher training is not built (the student trains: '
@@ -844,12 +857,14 @@ def main(argv=None):
         dt = (time.time() - t_) / 100
         log(f'render_func(model, pose): {dt * 1e3:.3f} ms per {H}x{W} frame over 100 runs ({H * W / dt:.3e} rays/s)')
         return 0
+    lpips = LPIPS(args.lpips_tensors) if args.lpips_tensors is not None and rank == 0 and gt is not None else None
     log('RENDER ONLY')
     t_ = time.time()
     st = {}
     with torch.no_grad():
         rgbs, misc = render_path(poses, hwf, kind, eng, gt_imgs=gt, savedir=outdir, log=log, given_rays=given, stats=st,
-                                 frames_per_batch=args.frames_per_batch or None, watch_every=args.watch_every, test_flip=args.test_flip)
+                                 frames_per_batch=args.frames_per_batch or None, watch_every=args.watch_every, test_flip=args.test_flip,
+                                 lpips=lpips)
     dt = time.time() - t_
     if rank == 0:
         np.save(os.path.join(outdir, 'rgbs.npy'), st['host_frames'].numpy() if 'host_frames' in st else rgbs.cpu().numpy())
@@ -871,6 +886,7 @@ def main(argv=None):
                 f"{ {k: float('%.2e' % v) for k, v in w_['worst'].items()} }, {len(w_['fallbacks'])} fallback(s); mode at the end: {w_['precision']}")
         if 'test_psnr' in misc:
             log(f"[TEST] TestPSNR {misc['test_psnr']:.4f} TestPSNRv2 {misc['test_psnr_v2']:.4f} "
-                f"TestSSIM {misc['test_ssim']:.4f}" + (f" TestFLIP {misc['test_flip']:.4f}" if 'test_flip' in misc else ''))
+                f"TestSSIM {misc['test_ssim']:.4f}" + (f" TestLPIPS {misc['test_lpips']:.4f}" if 'test_lpips' in misc else '') +
+                (f" TestFLIP {misc['test_flip']:.4f}" if 'test_flip' in misc else ''))
         log(f'Save renders: "{outdir}"')
     return 0

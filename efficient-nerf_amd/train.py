@@ -509,11 +509,11 @@ def load_test_split(args, device=None):
     return (poses, (int(hwf[0]), int(hwf[1]), float(hwf[2])), gt if device is None else gt.to(device)), None
 
 
-def eval_test_split(trainer, test, savedir=None, test_flip=False):
+def eval_test_split(trainer, test, savedir=None, test_flip=False, lpips=None):
     """render_path over the test split from the live weights (main.py:1442-1456): the frames [N, H, W, 3] on the device and
     frontend.test_metrics' test_psnr, test_psnr_v2 and test_ssim; with savedir the frames as <k>.png.  test: load_test_split's,
     its ground truth on the trainer's device."""
-    from .frontend import frame_errors, stack_flip, test_metrics, to8b, write_png
+    from .frontend import frame_errors, stack_flip, stack_lpips, test_metrics, to8b, write_png
     poses, (H, W, focal), gt = test
     rgbs = torch.empty((len(poses), H, W, 3), dtype=torch.float32, device=trainer.device)
     if gt.device != rgbs.device:
@@ -525,6 +525,8 @@ def eval_test_split(trainer, test, savedir=None, test_flip=False):
         mse_dev.append(mse)
         ssim_dev.append(ssim)
     misc = test_metrics(rgbs, gt, mse_dev, ssim_dev)
+    if lpips is not None:       # a metrics.LPIPS: reads the frames, writes buffers of its own
+        misc['test_lpips'] = stack_lpips(lpips, rgbs, gt)
     if test_flip:               # reads the frames, writes buffers of its own
         misc['test_flip'] = stack_flip(rgbs, gt)
     if savedir is not None:
@@ -552,6 +554,9 @@ def _train(args, log, engines):
     from .create_data import BlenderDataset_v2
     from .dist import rank_world, row_shard
     from .frontend import load_checkpoint
+    from .metrics import LPIPS, lpips_weights_from_args
+    # --test_lpips: refused, or its weights loaded once, before a device is touched (main() has done it already)
+    lpips_tensors = args.lpips_tensors if hasattr(args, 'lpips_tensors') else lpips_weights_from_args(args)
     rank, world = rank_world()       # several ranks: the loop is replicated, the rays of a step are sharded (ShardedStep)
     if rank != 0:
         log = lambda *a, **k: None
@@ -590,6 +595,10 @@ def _train(args, log, engines):
         test, missing = None, 'rank 0 renders the test split'
     has_test = test is not None
     flip_on = bool(getattr(args, 'test_flip', False))          # TestFLIP behind TestSSIM (main.py:1468)
+    lpips = None                                               # TestLPIPS between them: the context is created once, on the rank that renders
+    if lpips_tensors is not None and test is not None:
+        with torch.cuda.device(dev):
+            lpips = LPIPS(lpips_tensors)
     if world > 1:                # the other ranks enter the agreement guard where rank 0 renders
         import torch.distributed as td
         flag = [has_test]
@@ -625,9 +634,9 @@ def _train(args, log, engines):
             (f'rendered every {args.i_testset} iterations' if args.i_testset else 'not rendered while training (--i_testset 0)'))
     if args.test_pretrained and rank == 0:                    # main.py:1035-1047
         log('Testing pretrained...')
-        _, misc = eval_test_split(trainer, test, test_flip=flip_on)
+        _, misc = eval_test_split(trainer, test, test_flip=flip_on, lpips=lpips)
         log(f"Pretrained test: TestPSNR {misc['test_psnr']:.4f} TestPSNRv2 {misc['test_psnr_v2']:.4f}" +
-            (f" TestFLIP {misc['test_flip']:.4f}" if flip_on else ''))
+            (f" TestLPIPS {misc['test_lpips']:.4f}" if lpips is not None else '') + (f" TestFLIP {misc['test_flip']:.4f}" if flip_on else ''))
     order = None if online else _infinite_order(len(dataset))
 
     def draw(i):
@@ -650,8 +659,8 @@ def _train(args, log, engines):
 
     def test_pass(i):                         # main.py:1442-1456
         testsavedir = os.path.join(expdir, f'testset_iter{i}')
-        _, misc = eval_test_split(trainer, test, savedir=testsavedir, test_flip=flip_on)
-        flip_field = f"TestFLIP {misc['test_flip']:.4f} " if flip_on else ''
+        _, misc = eval_test_split(trainer, test, savedir=testsavedir, test_flip=flip_on, lpips=lpips)
+        flip_field = (f"TestLPIPS {misc['test_lpips']:.4f} " if lpips is not None else '') + (f"TestFLIP {misc['test_flip']:.4f} " if flip_on else '')
         return misc['test_psnr'], misc['test_psnr_v2'], f"TestSSIM {misc['test_ssim']:.4f} " + flip_field, f'Saved rendered test images: "{testsavedir}"'
 
     stepper, guard = trainer, None

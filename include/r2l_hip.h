@@ -549,6 +549,28 @@ int r2l_flip(const float* a_dev, const float* b_dev, int n_img, int H, int W, fl
  * point = P (x) G, first factor along x; 2 radius_feature + 1 taps). */
 int r2l_flip_taps(double pixels_per_degree, float* taps_host, int* radius_csf, int* radius_feature);
 
+/* ---- LPIPS of image pairs (csrc/r2l_lpips.hip; host side: efficient-nerf_amd/metrics.py LPIPS, load_lpips_weights) ----
+ * LPIPS v0.1 with the AlexNet trunk (the reference's default --lpips_net alex), the TestLPIPS of its [TEST] lines, on
+ * v = mul * (x - lo) + add of each image (three roundings, applied first; (0, 1, 0) is the identity, exactly; values are meant to lie
+ * in [-1, 1]): the scaling layer (v - shift) / scale, torchvision's features 0 .. 11 (conv 3->64 11x11 stride 4 pad 2, ReLU,
+ * max-pool 3x3 stride 2, conv 64->192 5x5 pad 2, ReLU, max-pool 3x3 stride 2, conv 192->384, 384->256, 256->256 3x3 pad 1, ReLU
+ * each; zero padding, floor-mode pooling), and per ReLU output k the mean over the pixels of sum_c lin_k[c] (n_a[c] - n_b[c])^2 with
+ * n = f / (sqrt(sum_c f_c^2) + 1e-10); d = sum_k d_k.  Symmetric in its two images; an identical pair gives 0.
+ * r2l_lpips_create copies 15 host tensors to the current device once: the 5 conv weights [out, in, kh, kw] as the state_dict holds
+ * them, the 5 biases, the 5 lin vectors [C_k] (C = 64, 192, 384, 256, 256), in this order.  a_dev, b_dev: float32 [n_img, H, W, 3];
+ * d_dev [n_img]: each pair's d; layers_dev [n_img, 5]: each pair's d_k, or NULL.  H and W from 31 (the second pool needs 3 rows and
+ * columns) to 32768: R2L_EINVAL beyond.  workspace_dev: r2l_lpips_workspace_floats(H, W) floats (or a negative code), whatever n_img:
+ * the pairs go through it in groups whose size follows from H and W alone (8 pairs of frames up to about 400 x 400, 1 pair from about
+ * 1100 x 1100).  The convolutions are a patch gather and the fp32 MFMA layer of r2l_linear_forward_dev;
+ * plain stores and fixed-order sums, no atomics: the same inputs give the same bits, a pair's value does not depend on n_img or on
+ * its place in the stack, and d is the same with and without layers_dev.  n_img = 0 is a no-op. */
+typedef struct r2l_lpips_ctx r2l_lpips_ctx;      /* the function below has the plain name */
+int r2l_lpips_create(r2l_lpips_ctx** out, const float* const* tensors_host, int n_tensors);
+void r2l_lpips_destroy(r2l_lpips_ctx* l);
+long long r2l_lpips_workspace_floats(int H, int W);
+int r2l_lpips(const r2l_lpips_ctx* l, const float* a_dev, const float* b_dev, int n_img, int H, int W, float a_lo, float a_mul, float a_add, float b_lo,
+              float b_mul, float b_add, float* d_dev, float* layers_dev, float* workspace_dev, long long workspace_floats, void* stream);
+
 /* ---- training of the NeRF teacher (csrc/nerf_train.hip; host mirror: efficient-nerf_amd/train_teacher.py) ----
  * A teacher step is the launches above (layers, embedding, scans, loss, Adam) plus the backward pass of nerf_raw2outputs[_noise]:
  * g_raw_dev [n,S,4] from g_rgb_map_dev [n,3], the only output the losses reach (main.py:728 detaches z_samples).  raw [n,S,4],
