@@ -12,6 +12,13 @@ Flags as the reference's (--splits a,b  --datadir  --suffix  --ignore i,j  --ful
 True and 4096 rays per shard are fixed as there, :97-98) plus --seed N (np.random.seed(N) in front of the two draws; without it the
 global stream as it stands, as the reference).  --donerf and the half resolution of non-square images (which the reference cannot
 run either: it hands cv2.resize (H, W) where (W, H) is expected, :173) are refused.
+
+    python convert_data.py --dataset_type llff --splits train --datadir data/nerf_llff_data/fern
+
+is the reference's utils/convert_original_data_to_rays_llff.py: the scene through llff.py (factor 8, every 8th view held out and
+4096 rays per shard are fixed there, :53-56, :80), train = the views that are not held out, val or test = the held-out ones, no
+halving and no compositing (the images are RGB), the same two permutation draws, the same dropped remainder, the same directory
+and file names; flags --splits --datadir --suffix --ignore (accepted and unused, as there) and --seed.
 """
 import argparse
 import ctypes as C
@@ -39,7 +46,10 @@ def parse_args(argv=None):
     p.add_argument('--donerf', action='store_true')
     p.add_argument('--full_res', action='store_true')
     p.add_argument('--seed', type=int, default=None, help='np.random.seed(N) in front of the two permutation draws')
+    p.add_argument('--dataset_type', type=str, default='blender', choices=['blender', 'llff'])
     args = p.parse_args(argv)
+    if args.dataset_type == 'llff' and (args.full_res or args.donerf):
+        raise SystemExit('--full_res / --donerf belong to --dataset_type blender: LLFF images are read at factor 8 and never halved')
     if args.donerf:
         raise SystemExit('--donerf: the DONERF ray rule is not built (rays are get_rays\', as for the Blender scenes)')
     if 'ficus' in args.datadir:
@@ -134,14 +144,49 @@ def rays_from_images(images, poses, focal, half_res, order, device=None):
     return out
 
 
+LLFF_FACTOR, LLFF_HOLD = 8, 8   # convert_original_data_to_rays_llff.py:56, :80
+
+
+def llff_views(n, splits):
+    """convert_original_data_to_rays_llff.py:90-105: the views of --splits in the order they are stacked -- the train views first
+    when 'train' is named, then the held-out ones once when 'val' or 'test' is"""
+    from . import llff
+    i_train, _, i_test = llff.split_indices(n, LLFF_HOLD)
+    views = []
+    if 'train' in splits:
+        views += [int(i) for i in i_train]
+    if 'val' in splits or 'test' in splits:
+        views += [int(i) for i in i_test]
+    return views
+
+
+def load_llff_images(datadir, splits):
+    """:79-107 with the images left as the PNGs' bytes: (uint8 [n, H, W, 3], float32 poses [n, 3, 4], (H, W, focal))"""
+    from . import llff
+    try:
+        scene = llff.load_scene(datadir, factor=LLFF_FACTOR, recenter_poses=True, bd_factor=.75, spherify=False, path_zflat=False, n_pose_video=120)
+    except llff.LLFFError as e:
+        raise SystemExit(str(e))
+    views = llff_views(len(scene.poses), splits)
+    if not views:
+        raise SystemExit(f'--splits {",".join(splits)} names no view of "{datadir}": train, val or test')
+    return np.ascontiguousarray(scene.bytes[views]), np.ascontiguousarray(scene.poses[views][:, :3, :4]), scene.hwf
+
+
 def convert(args, log=print):
     """the reference's script from its arguments on; returns the paths written"""
     splits, prefix, savedir = save_layout(args)
-    imgs, poses, angle = load_images(args.datadir, splits, args.ignore)
-    n_img, H0, W0, ch = imgs.shape
-    log(f'Read all images and poses, done. all_imgs shape {imgs.shape}, all_poses shape {poses.shape}')
-    half_res = not args.full_res
-    H, W, focal = output_grid(H0, W0, angle, half_res)
+    if getattr(args, 'dataset_type', 'blender') == 'llff':
+        imgs, poses, (H, W, focal) = load_llff_images(args.datadir, splits)
+        n_img, H0, W0, ch = imgs.shape
+        log(f'Read all images and poses, done. all_imgs shape {imgs.shape}, all_poses shape {poses.shape}')
+        half_res = False
+    else:
+        imgs, poses, angle = load_images(args.datadir, splits, args.ignore)
+        n_img, H0, W0, ch = imgs.shape
+        log(f'Read all images and poses, done. all_imgs shape {imgs.shape}, all_poses shape {poses.shape}')
+        half_res = not args.full_res
+        H, W, focal = output_grid(H0, W0, angle, half_res)
     os.makedirs(savedir, exist_ok=True)
     log(f'Resize, done. all_imgs shape {torch.Size([n_img, H, W, 3])}, all_poses shape {torch.Size(poses.shape)}, num_channels of the images {ch}')
     n = n_img * H * W

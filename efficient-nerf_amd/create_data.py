@@ -28,6 +28,14 @@ RNG: the reference draws everything from one `np.random.seed(0)` stream
 focal (create_data.py:816-818), two `permutation(n)` per saved group (:858-859), after
 `load_blender_data` has consumed 200 `get_rand_pose()` calls (load_blender.py:89-90).
 `RandStream` restates that consumption so the generated poses match the reference's.
+
+LLFF scenes (`--dataset_type llff`, the scene mounted under --datadir): intrinsics and poses come from llff.py; a random pose is
+get_rand_pose_v2's (dataset/load_llff.py:187-218: six draws, then one for the focal); the LLFF loader draws nothing, so
+`LLFFRandStream` consumes no loader draws.  The teacher is the NDC engine with near, far = 0, 1 and projects the rays of
+get_rays(H, W, focal_k, pose_k) with its own BASE focal: utils/create_data.py:819-831 passes `focal`, not `focal_`, to render,
+and the shards keep that.  The render is the deterministic teacher, as on Blender here: no jitter of the sample depths and no
+density noise, although the reference's LLFF configs set raw_noise_std (its create_data renders with the training kwargs) --
+the shards are reproducible, and the student is distilled from the teacher's mean prediction.
 """
 import ctypes as C
 import os
@@ -72,6 +80,19 @@ class RandStream:
                                                         out.ctypes.data_as(C.c_void_p)))
         self.rs.set_state((name, key, p.value, has_gauss, cached))
         return out
+
+
+class LLFFRandStream(RandStream):
+    """The same stream on an LLFF scene: no loader draws; a pose is llff.rand_pose's six draws (state: the loaded scene's
+    llff.RandPoseState), [3, 5] with the (H, W, focal) column the callers slice off"""
+
+    def __init__(self, state, seed=0):
+        super().__init__(seed, n_loader_poses=0)
+        self.state = state
+
+    def rand_pose(self):
+        from . import llff
+        return torch.from_numpy(llff.rand_pose(self.state, self.rs))
 
 
 def _npy_header(shape, dtype=np.float32):
@@ -277,6 +298,45 @@ def choose_precision_for_rand(engine, H, W, focal, use_rand_focal=True):
         ro, rd = get_rays(H, W, focal * (fs if use_rand_focal else 1.), pose_spherical(th, ph, 4.)[:3, :4], device=engine.device)
         sets.append((ro.reshape(-1, 3), rd.reshape(-1, 3)))
     return engine.choose_precision(sets)[0]
+
+
+#: probe poses of `--precision auto` on an LLFF scene: (fractions of the 1.1-scaled position box or None for the average pose, focal
+#: scale) -- the average pose and two opposite corners of the box get_rand_pose_v2 draws positions from, at focal x [1, 2)
+LLFF_RAND_PROBES = ((None, 1.0), ((0., 0., 0.), 1.5), ((1., 1., 1.), 2.0))
+
+
+def llff_probe_rays(state, H, W, focal, device, use_rand_focal=True):
+    from . import llff
+    sets = []
+    for corner, fs in LLFF_RAND_PROBES:
+        pose = state.c2w[:3, :4].astype(np.float32) if corner is None else llff.pose_in_boxes(state, corner, (.5, .5, .5))[:3, :4]
+        ro, rd = get_rays(H, W, focal * (fs if use_rand_focal else 1.), torch.from_numpy(np.ascontiguousarray(pose)), device=device)
+        sets.append((ro.reshape(-1, 3), rd.reshape(-1, 3)))
+    return sets
+
+
+def build_llff_teacher_engine(args, ckpt, hwf, state, use_rand_focal=True, log=None, watched='per save group'):
+    """build_teacher_engine for an LLFF scene: the NDC teacher with near, far = 0, 1 (main.py:917-919, 160-162) that renders
+    llff.rand_pose's poses at focal x [1, 2); `auto` measures on llff_probe_rays.  args.dataset_type is 'llff' without --no_ndc."""
+    from . import frontend as fe
+    from . import NeRFEngine, PRECISIONS
+    H, W, focal = hwf
+    if args.no_ndc:
+        raise SystemExit('--create_data rand on --dataset_type llff renders the NDC teacher: --no_ndc is not built here')
+    if fe.teacher_needs_generic(args):
+        args.model_name = 'nerf'
+        _, eng = fe.build_engine(args, (H, W, focal), ckpt, log=log)          # GenericNeRF(..., 0., 1., ndc=True)
+        return eng
+    auto = args.precision == 'auto'
+    eng = NeRFEngine(H, W, focal, 0., 1., N_samples=args.N_samples, N_importance=args.N_importance, ndc=True,
+                     white_bkgd=args.white_bkgd, precision=PRECISIONS['fp16x3' if auto else args.precision])
+    eng.load_state_dicts(ckpt['network_fn_state_dict'], ckpt['network_fine_state_dict'])
+    if auto:
+        name = eng.choose_precision(llff_probe_rays(state, H, W, focal, eng.device, use_rand_focal))[0]
+        if log:
+            log(f'[precision] auto: largest rgb / acc difference from fp16x3 on {min(4096, H * W):,} rays of each of {len(LLFF_RAND_PROBES)} probe poses '
+                f'(the average pose and two opposite corners of the position box, focal x 1 ... x 2): {eng.auto_diffs} -> {name}; watched {watched}')
+    return eng
 
 
 def _agree_failed(failed, world, dev):
@@ -580,7 +640,7 @@ def main(argv=None):
     --n_pose_kd N --datadir_kd old:new` (README.md:79 of the reference)."""
     import argparse
     from . import frontend as fe
-    ap = argparse.ArgumentParser(add_help=False)
+    ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)      # --datadir must reach the front end, not match --datadir_kd here
     ap.add_argument('--create_data', type=str, default='spiral_evenly_spaced')
     ap.add_argument('--teacher_ckpt', type=str, default='')
     ap.add_argument('--n_pose_kd', type=int, default=100)
@@ -598,11 +658,25 @@ def main(argv=None):
     rank, local_rank, world = D.init()
     torch.cuda.set_device(D.local_device(local_rank))
     ckpt = fe.load_checkpoint(own.teacher_ckpt)
-    _, (H, W, focal) = fe.load_test_poses(args)
-    eng = build_teacher_engine(args, ckpt, (H, W, focal), not own.no_rand_focal, log=print if rank == 0 else None)
+    stream = None
+    if args.dataset_type == 'llff' and args.synthetic_poses <= 0:      # (--synthetic_poses: the lego intrinsics and hemisphere, as before)
+        from . import llff
+        if not fe.has_llff_scene(args):
+            raise SystemExit(f'--create_data rand on --dataset_type llff draws its poses from the scene: "{os.path.join(args.datadir, "poses_bounds.npy")}" '
+                             f'is not there')
+        try:
+            scene = llff.load_scene(args.datadir, args.factor, spherify=args.spherify, n_pose_video=llff.n_pose_video_from_flag(args.n_pose_video))
+        except llff.LLFFError as e:
+            raise SystemExit(str(e))
+        H, W, focal = scene.hwf
+        eng = build_llff_teacher_engine(args, ckpt, (H, W, focal), scene.rand_state, not own.no_rand_focal, log=print if rank == 0 else None)
+        stream = LLFFRandStream(scene.rand_state)
+    else:
+        _, (H, W, focal) = fe.load_test_poses(args)
+        eng = build_teacher_engine(args, ckpt, (H, W, focal), not own.no_rand_focal, log=print if rank == 0 else None)
     tm = {}
     n = create_rand(eng, H, W, focal, own.n_pose_kd, own.datadir_kd.split(':')[1], not own.no_rand_focal,
-                    i_save=own.create_data_chunk, split_size=own.split_size, rm_existing_data=own.rm_existing_data,
+                    i_save=own.create_data_chunk, split_size=own.split_size, rm_existing_data=own.rm_existing_data, stream=stream,
                     log=print if rank == 0 else (lambda *a, **k: None), timings=tm)
     if rank == 0:
         print(f'wrote {n} shard(s) of {own.split_size} rays; {tm["poses"]} poses in {tm["wall_s"]:.2f} s = '

@@ -52,6 +52,8 @@ FLAGS = [
     ('--render_test', dict(action=_BOOL)), ('--render_factor', dict(type=int, default=0)),
     ('--dataset_type', dict(type=str, default='llff')), ('--testskip', dict(type=int, default=8)),
     ('--white_bkgd', dict(action=_BOOL)), ('--half_res', dict(action=_BOOL)), ('--no_ndc', dict(action=_BOOL)),
+    # LLFF scenes (llff.py; option.py:165-185): the `images_<factor>` folder, every llffhold-th view held out, --spherify refused
+    ('--factor', dict(type=int, default=8)), ('--llffhold', dict(type=int, default=8)), ('--spherify', dict(action=_BOOL)),
     ('--lindisp', dict(action=_BOOL)), ('--model_name', dict(type=str, default='nerf')),
     ('--n_sample_per_ray', dict(type=int, default=192)), ('--pretrained_ckpt', dict(type=str, default='')),
     ('--n_pose_video', dict(type=str, default='20,4,1')), ('--video_tag', dict(type=str, default='')),
@@ -284,12 +286,40 @@ def load_test_poses(args):
     return poses, (H, W, focal)
 
 
+def has_llff_scene(args):
+    """--dataset_type llff with the scene mounted (poses_bounds.npy under --datadir) and no --synthetic_poses: poses, intrinsics
+    and images come from llff.py; every other llff command line keeps the synthetic poses"""
+    from . import llff
+    return args.dataset_type == 'llff' and args.synthetic_poses <= 0 and llff.has_scene(args.datadir)
+
+
+def llff_test_views(args):
+    """main.py:891-911, 1005: (scene, i_test) -- the loaded scene and its held-out views (every --llffhold-th; the loader's own
+    single view nearest the average pose when --llffhold is 0)"""
+    from . import llff
+    scene = llff.load_scene(args.datadir, args.factor, spherify=args.spherify, n_pose_video=llff.n_pose_video_from_flag(args.n_pose_video))
+    i_test = llff.split_indices(len(scene.poses), args.llffhold)[2] if args.llffhold > 0 else np.array([scene.i_test])
+    return scene, i_test
+
+
+def load_llff_set(args):
+    """The LLFF branch of load_test_set: with --render_test the held-out views' poses [n, 3, 4], (H, W, focal) of the loader's
+    first pose and their images; without it the loader's spiral path (main.py:1011) and no ground truth.  No --testskip, no
+    compositing: the images are RGB."""
+    scene, i_test = llff_test_views(args)
+    if args.render_test:
+        return torch.from_numpy(scene.poses[i_test][:, :3, :4].copy()), scene.hwf, torch.from_numpy(scene.images[i_test])
+    return torch.from_numpy(scene.render_poses[:, :3, :4].copy()), scene.hwf, None
+
+
 def load_test_set(args):
     """--render_test with a mounted Blender scene (main.py:922-937, 1004-1012): the test split's
     poses, intrinsics and ground-truth RGB (composited on white with --white_bkgd).  Returns
     (poses, (H, W, focal), gt [N,H,W,3] or None); falls back to `load_test_poses` (no GT) when the
-    scene's images are not there."""
+    scene's images are not there.  A mounted LLFF scene: load_llff_set."""
     from . import blender
+    if has_llff_scene(args):
+        return load_llff_set(args)
     tf = os.path.join(args.datadir, 'transforms_test.json')
     if args.synthetic_poses > 0 or args.dataset_type != 'blender' or not os.path.exists(tf):
         return load_test_poses(args) + (None,)
@@ -366,10 +396,12 @@ def teacher_needs_generic(args):
             or (args.netdepth, args.netwidth, args.netdepth_fine, args.netwidth_fine) != (8, 256, 8, 256) or args.precision == 'fp32')
 
 
-def build_engine(args, hwf, ckpt, probe_pose=None, probe_rays=None, log=None, probe_poses=None):
+def build_engine(args, hwf, ckpt, probe_pose=None, probe_rays=None, log=None, probe_poses=None, bounds=None):
     """Engine for the flags of the reference command line.  Every flag that changes what the reference network
     computes is either honoured or refused: a checkpoint trained with another activation / res_scale / depth must
-    not render silently wrong images (ResMLP honours them: model/nerf_raybased.py:443-465)."""
+    not render silently wrong images (ResMLP honours them: model/nerf_raybased.py:443-465).
+    bounds: (near, far) the caller computed while loading an LLFF scene (main.py:917-919 hands them to create_nerf and the
+    PointSampler, :1001); an LLFF student is built only with them, because its poses must be the loader's."""
     from . import NeRFEngine, PRECISIONS, R2LEngine, R2LError
     H, W, focal = hwf
     auto = args.precision == 'auto'
@@ -381,7 +413,7 @@ def build_engine(args, hwf, ckpt, probe_pose=None, probe_rays=None, log=None, pr
     if args.dataset_type == 'blender':
         near, far = 2., 6.  # main.py:930-931
     elif llff_ndc:
-        near, far = 0., 1.  # main.py:917-918
+        near, far = (0., 1.) if bounds is None else (float(b) for b in bounds)  # main.py:917-918
     elif args.trial.near > 0 and args.trial.far > 0:
         near = far = None   # taken from --trial.near / --trial.far below
     else:
@@ -393,7 +425,12 @@ def build_engine(args, hwf, ckpt, probe_pose=None, probe_rays=None, log=None, pr
         far = args.trial.far
     if args.model_name in ('R2L', 'nerf_v3.2'):
         if llff_ndc:
-            raise R2LError('the R2L path is built for world-space rays (blender / --no_ndc)')
+            # main.py:917-919, 1001; model/nerf_raybased.py:94-102: the student on LLFF samples world-space rays at depths in [0, 1] -- in
+            # the loader's rescaled, recentred frame, so only poses of a loaded scene make sense (lego-circle poses would render nonsense)
+            if bounds is None:
+                raise R2LError('an R2L student on --dataset_type llff renders the poses of a loaded scene (near, far = 0, 1 in the loader\'s '
+                               'rescaled, recentred frame): mount the scene (poses_bounds.npy under --datadir, no --synthetic_poses), or pass --no_ndc '
+                               'with --trial.near / --trial.far')
         if args.plucker or args.learn_depth or args.linear_tail:
             raise R2LError('plucker / learn_depth / linear_tail variants are not built (linear_tail: the reference builds Linear(input_dim, 3) '
                            'on the body output and cannot run it either, model/nerf_raybased.py:532-537)')
@@ -819,8 +856,15 @@ def main(argv=None):
     ckpt = load_checkpoint(args.pretrained_ckpt)
     log(f'Load pretrained ckpt successfully: "{args.pretrained_ckpt}".')
     gt = None
-    if args.render_test:
-        poses, hwf, gt = load_test_set(args)
+    bounds = None
+    if args.render_test or has_llff_scene(args):
+        from .llff import LLFFError
+        try:
+            poses, hwf, gt = load_test_set(args)
+        except LLFFError as e:                # the loader's refusals are one line each
+            raise SystemExit(str(e))
+        if has_llff_scene(args) and not args.no_ndc:
+            bounds = (0., 1.)                 # main.py:917-919
     else:
         poses, hwf = load_test_poses(args)
     given = None
@@ -838,7 +882,7 @@ def main(argv=None):
     kind, eng = build_engine(args, hwf, ckpt, probe_pose=None if given is not None else poses[0][:3, :4],
                              probe_rays=None if given is None else (given[0][0].reshape(-1, 3), given[1][0].reshape(-1, 3)),
                              probe_poses=None if given is not None else [poses[k][:3, :4] for k in sorted({0, len(poses) // 2, len(poses) - 1})],
-                             log=log)
+                             log=log, bounds=bounds)
     outdir = args.outdir or os.path.join(args.basedir, args.expname or 'render', 'gen_img')
     if rank == 0:
         os.makedirs(outdir, exist_ok=True)

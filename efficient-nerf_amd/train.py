@@ -9,6 +9,7 @@ that are added in a fixed order, not with atomics).
 
 The network description is generic.v3_2_plan's: every shape the reference's constructor accepts.
 """
+import argparse
 import json
 import math
 import os
@@ -469,6 +470,8 @@ def run_iterations(args, trainer, start, best, weights_dir, log, *, draw, after_
 def trainer_from_args(args, max_rays):
     if args.dataset_type == 'blender':
         near, far = 2., 6.          # main.py:930-931
+    elif args.dataset_type == 'llff' and not args.no_ndc:
+        near, far = 0., 1.          # main.py:917-919: the student samples world-space rays of the loader's frame at depths in [0, 1]
     elif args.trial.near > 0 and args.trial.far > 0:
         near, far = args.trial.near, args.trial.far
     else:
@@ -493,8 +496,17 @@ def load_test_split(args, device=None):
     [N, H, W, 3] on `device`), None), or (None, what is missing) when there is no test split to load.  A transforms_test.json
     whose images are not there is an error: a half-copied scene must not train without the validation it asked for."""
     from . import blender
+    if args.dataset_type == 'llff':      # main.py:891-911, 1005: the held-out views of the scene under --datadir
+        from .frontend import has_llff_scene, load_llff_set
+        if not has_llff_scene(args):
+            return None, (f'"{os.path.join(args.datadir, "poses_bounds.npy")}" (--dataset_type llff' +
+                          (', and --synthetic_poses is set' if args.synthetic_poses > 0 else '') + ')')
+        view = argparse.Namespace(**vars(args))
+        view.render_test = True
+        poses, hwf, gt = load_llff_set(view)
+        return (poses, hwf, gt if device is None else gt.to(device)), None
     if args.dataset_type != 'blender':
-        return None, f'--dataset_type {args.dataset_type} (test renders are built for --dataset_type blender)'
+        return None, f'--dataset_type {args.dataset_type} (test renders are built for --dataset_type blender and llff)'
     tf = os.path.join(args.datadir, 'transforms_test.json')
     if not os.path.exists(tf):
         return None, f'"{tf}"'
