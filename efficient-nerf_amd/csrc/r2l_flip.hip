@@ -10,7 +10,9 @@
 //   flip_cols_kernel     one block = a 64 x 32 tile of the pair.  Plane by plane it stages tile + halo rows (rows clamped) in one 16 KiB
 //                        LDS buffer; a thread owns 8 consecutive rows of one column and slides down it, so an LDS read feeds 8 (or 16)
 //                        FMAs: taps come from the kernel arguments through the scalar unit, padded with 7 zeros on both sides so that
-//                        the slide needs no bounds test.  Then the colour pipeline (clamped linear RGB -> L*a*b* -> Hunt -> HyAB ->
+//                        the slide needs no bounds test (sums that come out NaN are taken again over their own rows: 0 * NaN would
+//                        carry a NaN pixel further than the reference's filters do).  Then the colour pipeline (clamped linear RGB ->
+//                        L*a*b* -> Hunt -> HyAB ->
 //                        redistribution), the feature pipeline and dE_c ^ (1 - dE_f) per pixel; a plain store into the map and one
 //                        partial sum per block (fixed-order tree).
 //   flip_mean_kernel     one block per frame adds the partials in a fixed order in float64: frame_mean.
@@ -144,6 +146,23 @@ __device__ __forceinline__ void filter_column(float (*tile)[FLIP_TILE_W], const 
         for (int o = 0; o < FLIP_PER_THREAD; ++o) {
             acc0[o] = fmaf(t0[FLIP_PAD + j - o], v, acc0[o]);
             if (NF == 2) acc1[o] = fmaf(t1[FLIP_PAD + j - o], v, acc1[o]);
+        }
+    }
+    // 0 * NaN is NaN: a NaN in any row of the window has gone into all eight sums through the padding, also into those whose filter
+    // does not reach that row, where the reference's dense filter leaves the pixel finite.  A sum that came out NaN is taken again
+    // over its own rows o .. o + 2 R alone, in the same order.  Every row of the window meets every sum (with a tap or a zero), so
+    // one sum is NaN exactly when all are: frames without a NaN pay one comparison per plane.
+    if (acc0[0] != acc0[0]) {
+#pragma unroll
+        for (int o = 0; o < FLIP_PER_THREAD; ++o) {
+            float s0 = 0.f, s1 = 0.f;
+            for (int j = o; j <= o + 2 * R; ++j) {
+                const float v = tile[l0 + j][tx];
+                s0 = fmaf(t0[FLIP_PAD + j - o], v, s0);
+                if (NF == 2) s1 = fmaf(t1[FLIP_PAD + j - o], v, s1);
+            }
+            acc0[o] = s0;
+            if (NF == 2) acc1[o] = s1;
         }
     }
 }

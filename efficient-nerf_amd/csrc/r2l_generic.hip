@@ -35,7 +35,7 @@ struct r2l_linear {
 
 __device__ __forceinline__ float r2l_generic_act(float v, int act) {
     switch (act) {
-        case R2L_ACT_RELU: return fmaxf(v, 0.0f);
+        case R2L_ACT_RELU: return (v != v) ? v : fmaxf(v, 0.0f);      // nn.ReLU: a NaN stays a NaN (fmaxf alone returns the 0)
         case R2L_ACT_LRELU: return v > 0.0f ? v : 0.01f * v;      // nn.LeakyReLU default slope
         case R2L_ACT_SIGMOID: return 1.0f / (1.0f + expf(-v));
         default: return v;

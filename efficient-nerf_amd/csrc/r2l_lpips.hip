@@ -7,8 +7,9 @@
 //                         r2l_lpips_create reorders the state_dict's [out, in, kh, kw] once on the host to match -- zeros where the
 //                         window leaves the image.  The first layer's gather also applies v = mul (x - lo) + add and the scaling
 //                         layer (v - shift) / scale.
-//   r2l_linear_forward_dev  the library's fp32 MFMA layer (csrc/r2l_generic.hip): patches x weight^T + bias, ReLU.  A row's sum does not
-//                         depend on where the row stands, so a pair's value does not depend on its place in the stack.
+//   r2l_linear_forward_dev  the library's fp32 MFMA layer (csrc/r2l_generic.hip): patches x weight^T + bias, ReLU (a NaN stays a NaN, as
+//                         in nn.ReLU).  A row's sum does not depend on where the row stands, so a pair's value does not depend on its
+//                         place in the stack, and a NaN pixel reaches its own pair alone.
 //   lpips_pool_kernel     max over 3 x 3 windows, stride 2, no padding, floor mode; one block = one output pixel.
 //   lpips_dist_kernel     one wave = one pixel at a time: both images' feature vectors are normalised over the channels,
 //                         n = f / (sqrt(sum f^2) + 1e-10), and sum_c lin[c] (n_a[c] - n_b[c])^2 is taken; the sums run in float64

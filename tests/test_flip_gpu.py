@@ -6,7 +6,17 @@ The yardstick is tests/golden/flip.npz (make_golden_flip.py): the reference's ow
 float32 evaluations can each sit one band from exact, and the separable summation order gets the other factor of two.  The band a
 case is held to is the largest among the plain natural-image cases at its pixels_per_degree (one 5 x 7 case's own band is too lucky
 a sample), or its own where that is larger (the rescaled pair, whose dark half is the more sensitive input); white against black,
-an input of another kind, is held to its own.  No pixel is excluded."""
+an input of another kind, is held to its own.  No pixel is excluded.
+
+tests/golden/flip_edges.npz (make_golden_flip_edges.py) holds the same for the edges of the kernels' tiles and radii, EDGES below:
+natural pairs at pixels_per_degree 118 (radii 16 and 15, the largest the kernels accept: the column kernel's 64-row LDS tile, the row
+kernel's 160-wide rows and the padded tap rows are used to their last element), 5 (radii 1 and 1) and 16 (3 and 2), as one-pixel
+strips, a frame smaller than every filter, exact multiples of the 64 x 32 and 128 x 2 tiles and one pixel past them; same rule, the
+band the largest among the edge cases at the same pixels_per_degree.  Its last case has one NaN and one +Inf pixel: the map's NaN
+set must be the reference's (the 21 x 21 box the dense filters reach from the NaN pixel; the column pass slides eight outputs over
+zero-padded taps and 0 * NaN is NaN, so it has to sum such outputs again over their own rows), the finite pixels are held to the
+rule, the mean is NaN with and without a map, and the Inf is clamped to 1 as the reference clamps it."""
+import ctypes as C
 import json
 import os
 import re
@@ -22,6 +32,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NATURAL = (0, 1, 2, 3, 4, 8, 9, 10)          # plain natural-image pairs (make_golden_flip.py); 5 identical, 6 white / black, 7 rescaled
 IDENTICAL, WHITE_BLACK, RESCALED = 5, 6, 7
 N_CASES = 11
+# flip_edges.npz: (pixels_per_degree, (CSF radius, feature radius), (H, W)) of its natural pairs, then the NaN / Inf pair
+EDGES = [(118.0, (16, 15), hw) for hw in ((1, 70), (70, 1), (3, 5), (32, 64), (32, 128), (33, 129))] + \
+        [(5.0, (1, 1), hw) for hw in ((3, 5), (1, 70), (33, 129))] + [(16.0, (3, 2), hw) for hw in ((70, 1), (32, 64))]
+NAN_CASE, NAN_BOX = len(EDGES), (slice(10, 31), slice(20, 41))          # a[20, 30, 1] = NaN at radii (10, 9)
 
 
 @pytest.fixture(scope='module')
@@ -39,6 +53,24 @@ def _band(golden, k):
         return float(golden[f'band_{k}'])
     group = max(float(golden[f'band_{j}']) for j in NATURAL if float(golden[f'ppd_{j}']) == float(golden[f'ppd_{k}']))
     return max(group, float(golden[f'band_{k}']))
+
+
+@pytest.fixture(scope='module')
+def edges(golden_dir):
+    return np.load(os.path.join(golden_dir, 'flip_edges.npz'))
+
+
+def _edge_case(edges, k):
+    return (torch.tensor(edges[f'a_{k}'].astype(np.float32)).cuda()[None], torch.tensor(edges[f'b_{k}'].astype(np.float32)).cuda()[None],
+            float(edges[f'ppd_{k}']))
+
+
+def _radii(ppd):
+    """the filter radii the library builds its taps for at `ppd`"""
+    from efficient_nerf_amd import _lib
+    buf, rc, rf = (C.c_float * (7 * 33))(), C.c_int(), C.c_int()
+    _lib.check(_lib.lib().r2l_flip_taps(float(ppd), buf, C.byref(rc), C.byref(rf)))
+    return rc.value, rf.value
 
 
 @pytest.mark.parametrize('k', range(N_CASES))
@@ -61,10 +93,8 @@ def test_golden_case(pkg, built_lib, golden, k):
     assert err <= 4 * band and err_mean <= 4 * band
 
 
-def test_stacks_have_no_halo_and_runs_repeat(pkg, built_lib, golden):
-    """three frames in one call = three calls, bit for bit; no map = the same means; twice = the same bits"""
+def _stack_checks(a0, b0, ppd):
     from efficient_nerf_amd import _lib, metrics
-    a0, b0, ppd, _ = _case(golden, 3)
     a = torch.cat([a0, b0.flip(1), a0.flip(2) * 0.5], 0).contiguous()
     b = torch.cat([b0, a0.flip(1) * 0.9, b0.flip(2) * 0.5 + 0.1], 0).contiguous()
     n, H, W = a.shape[:3]
@@ -92,6 +122,79 @@ def test_stacks_have_no_halo_and_runs_repeat(pkg, built_lib, golden):
     assert torch.equal(call(b, a)[0], fmap)                            # symmetric in its two images
     assert abs(metrics.flip(a, b, pixels_per_degree=ppd) - float(means.double().mean())) == 0.0
     assert L.r2l_flip(None, None, 0, H, W, 0., 1., 0., 0., 1., 0., ppd, None, None, None, 0, None) == 0
+
+
+def test_stacks_have_no_halo_and_runs_repeat(pkg, built_lib, golden):
+    """three frames in one call = three calls, bit for bit; no map = the same means; twice = the same bits"""
+    a0, b0, ppd, _ = _case(golden, 3)
+    _stack_checks(a0, b0, ppd)
+
+
+def test_stacks_at_the_largest_radius(pkg, built_lib, edges):
+    """the same on three 33 x 129 frames at radii (16, 15), through a NaN-filled workspace of exactly the reported size"""
+    k = EDGES.index((118.0, (16, 15), (33, 129)))
+    a0, b0, ppd = _edge_case(edges, k)
+    assert _radii(ppd) == (16, 15) and tuple(a0.shape[1:3]) == (33, 129)
+    _stack_checks(a0, b0, ppd)
+
+
+@pytest.mark.parametrize('k', range(len(EDGES)))
+def test_edge_case(pkg, built_lib, edges, k):
+    """map and mean of every natural pair of flip_edges.npz against the reference's float64 result, at the radii EDGES names"""
+    from efficient_nerf_amd import metrics
+    want_ppd, radii, shape = EDGES[k]
+    a, b, ppd = _edge_case(edges, k)
+    want = edges[f'map64_{k}']
+    assert ppd == want_ppd and want.shape == shape and _radii(ppd) == radii
+    mean, fmap = metrics.flip(a, b, pixels_per_degree=ppd, return_map=True)
+    got = fmap[0].cpu().numpy().astype(np.float64)
+    assert got.shape == want.shape
+    band = max(float(edges[f'band_{j}']) for j in range(len(EDGES)) if EDGES[j][0] == want_ppd)
+    err, err_mean = np.abs(got - want).max(), abs(mean - float(edges[f'mean64_{k}']))
+    print(f'edge case {k} {shape} pixels_per_degree {ppd:.2f} radii {radii}: L_inf {err:.3e} = {err / band:.2f} band ({band:.2e}), mean off by '
+          f'{err_mean:.3e} = {err_mean / band:.2f} band (mean {mean:.6f})')
+    assert np.isfinite(got).all()
+    assert err <= 4 * band and err_mean <= 4 * band
+
+
+def test_a_nan_pixel_reaches_the_reference_s_box_and_an_inf_is_clamped(pkg, built_lib, golden, edges):
+    """a[20, 30, 1] = NaN, b[5, 5, 0] = +Inf at radii (10, 9): NaN exactly where the reference's map is NaN, the other pixels within
+    the band, a NaN mean, the same mean bits with and without a map"""
+    from efficient_nerf_amd import _lib, metrics
+    a, b, ppd = _edge_case(edges, NAN_CASE)
+    want = edges[f'map64_{NAN_CASE}']
+    nan = np.isnan(want)
+    box = np.zeros(want.shape, dtype=bool)
+    box[NAN_BOX] = True
+    assert _radii(ppd) == (10, 9) and want.shape == (48, 56) and np.array_equal(nan, box) and np.isnan(float(edges[f'mean64_{NAN_CASE}']))
+    assert torch.isnan(a).sum() == 1 and torch.isinf(b).sum() == 1
+    mean, fmap = metrics.flip(a, b, pixels_per_degree=ppd, return_map=True)
+    got_nan = torch.isnan(fmap[0]).cpu().numpy()
+    got = fmap[0].cpu().numpy().astype(np.float64)
+    rows, cols = np.flatnonzero(got_nan.any(1)), np.flatnonzero(got_nan.any(0))
+    band = max([float(edges[f'band_{NAN_CASE}'])] + [float(golden[f'band_{j}']) for j in NATURAL if float(golden[f'ppd_{j}']) == ppd])
+    err = np.abs(got - want)[~nan & ~got_nan].max()
+    print(f'NaN case: {int(got_nan.sum())} NaN pixels in rows {rows.min()} .. {rows.max()}, columns {cols.min()} .. {cols.max()} (the reference: '
+          f'{int(nan.sum())} in rows 10 .. 30, columns 20 .. 40); finite pixels L_inf {err:.3e} = {err / band:.2f} band ({band:.2e}); mean {mean}')
+    assert np.array_equal(got_nan, nan)
+    assert err <= 4 * band
+    assert np.isnan(mean)
+    assert np.array_equal(torch.isnan(metrics.flip(b, a, pixels_per_degree=ppd, return_map=True)[1][0]).cpu().numpy(), nan)
+    L = _lib.lib()
+    H, W = want.shape
+    need = L.r2l_flip_workspace_floats(H, W, ppd)
+    means = []
+    for with_map in (True, False):
+        ws = torch.full((need,), float('nan'), device='cuda')
+        out = torch.full((1, H, W), -1., device='cuda') if with_map else None
+        m = torch.full((1,), -1., device='cuda')
+        _lib.check(L.r2l_flip(_lib.dptr(a), _lib.dptr(b), 1, H, W, 0., 1., 0., 0., 1., 0., ppd, _lib.dptr(out), _lib.dptr(m), _lib.dptr(ws), need,
+                              _lib.current_stream()))
+        torch.cuda.synchronize()
+        means.append(m)
+        if with_map:
+            assert torch.equal(out.view(torch.int32), fmap.view(torch.int32))
+    assert torch.isnan(means[0]).all() and torch.equal(means[0].view(torch.int32), means[1].view(torch.int32))
 
 
 def test_identity_constants_equal_premapped_copies(pkg, built_lib, golden):

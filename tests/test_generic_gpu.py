@@ -3,7 +3,11 @@ the layer op against torch's F.linear on the same inputs, the sampler / embedder
 variants the fused kernels refuse against golden vectors from the reference's own classes.
 
 Tolerances: points bit-exact (one rounding per op, as the reference); embeddings <= 5e-7; a layer <= 2e-5 x max|y| (fp32
-products, fp32 accumulation: only the summation order differs from the CPU's); rgb <= 1e-4 (BASELINE.json's contract; measured ~1e-6)."""
+products, fp32 accumulation: only the summation order differs from the CPU's); rgb <= 1e-4 (BASELINE.json's contract; measured ~1e-6).
+
+NaN and infinity go through a layer as they go through F.linear and the activation on the CPU: a NaN in x or res makes NaN exactly
+the outputs it makes NaN there (nn.ReLU passes a NaN on, so the kernel's ReLU must: fmaxf(NaN, 0) alone is 0) and leaves every other
+output its bits; ReLU of -inf and of 0 is +0."""
 import json
 import os
 
@@ -59,6 +63,55 @@ def test_linear_layer_matches_torch(pkg, n, in_dim, out_dim, act, res, post):
         y2 = r.cuda().clone()
         lin(x.cuda(), y2, act=act, res=y2, res_scale=0.3, post=None if p is None else p.cuda())
         assert torch.equal(y2, got.contiguous())
+
+
+@pytest.mark.parametrize('where', ['x', 'res'])
+@pytest.mark.parametrize('act', ['none', 'relu', 'lrelu', 'sigmoid'])
+def test_a_nan_goes_where_torch_sends_it(pkg, act, where):
+    """one NaN element in x (its row of y) or in res (its element of y): NaN exactly where F.linear + activation gives NaN on the
+    CPU, every other output bit-equal to the call without the NaN; two row tiles (129 rows), the NaN in the first"""
+    from efficient_nerf_amd.generic import Linear
+    n, in_dim, out_dim, row, col = 129, 319, 256, 70, 200
+    gen = torch.Generator().manual_seed(n + in_dim)
+    x = torch.randn(n, in_dim, generator=gen)
+    w = (torch.rand(out_dim, in_dim, generator=gen) * 2 - 1) / in_dim ** 0.5
+    b = torch.rand(out_dim, generator=gen) - 0.5
+    r = torch.randn(n, out_dim, generator=gen)
+    lin = Linear(w, b)
+    call = lambda x_, r_: lin(x_.cuda(), torch.empty(n, out_dim, device='cuda'), act=act, res=r_.cuda(), res_scale=0.3).cpu()
+    clean = call(x, r)
+    assert torch.isfinite(clean).all()
+    x_nan, r_nan = x.clone(), r.clone()
+    (x_nan if where == 'x' else r_nan)[row, col] = float('nan')
+    want_nan = torch.isnan(ref_layer(x_nan, w, b, act, r_nan, 0.3, None))
+    expect = torch.zeros(n, out_dim, dtype=torch.bool)
+    if where == 'x':
+        expect[row] = True
+    else:
+        expect[row, col] = True
+    assert torch.equal(want_nan, expect)                        # what torch does, stated
+    got = call(x_nan, r_nan)
+    print(f'{act}, NaN in {where}: {int(torch.isnan(got).sum())} NaN outputs, torch {int(want_nan.sum())}')
+    assert torch.equal(torch.isnan(got), want_nan)
+    assert torch.equal(got[~want_nan].view(torch.int32), clean[~want_nan].view(torch.int32))
+
+
+def test_relu_of_minus_infinity_and_of_zero_is_zero(pkg):
+    """a bias of -inf: exactly -inf in front of the ReLU, +0 behind it; a zero weight row without bias: +0; a bias of +inf stays"""
+    from efficient_nerf_amd.generic import Linear
+    n, in_dim, out_dim = 129, 319, 256
+    gen = torch.Generator().manual_seed(5)
+    x = torch.randn(n, in_dim, generator=gen)
+    w = (torch.rand(out_dim, in_dim, generator=gen) * 2 - 1) / in_dim ** 0.5
+    b = torch.rand(out_dim, generator=gen) - 0.5
+    w[3], b[3], b[7], b[9] = 0., 0., float('-inf'), float('inf')
+    want = ref_layer(x, w, b, 'relu', None, 1.0, None)
+    assert torch.all(want[:, [3, 7]] == 0) and torch.all(want[:, 9] == float('inf'))
+    got = Linear(w, b)(x.cuda(), torch.empty(n, out_dim, device='cuda'), act='relu').cpu()
+    assert torch.all(got[:, [3, 7]].contiguous().view(torch.int32) == 0)          # +0, bit for bit
+    assert torch.all(got[:, 9] == float('inf')) and not torch.isnan(got).any()
+    rest = [o for o in range(out_dim) if o not in (3, 7, 9)]
+    assert (got[:, rest] - want[:, rest]).abs().max().item() <= 2e-5 * max(1.0, want[:, rest].abs().max().item())
 
 
 def test_layer_refuses_bad_arguments(pkg):

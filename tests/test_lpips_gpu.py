@@ -9,7 +9,15 @@ one pair of each stack with b = a).  The kernels and the float32 oracle are both
 kernels' d and every d_k may sit 8 x the float32 oracle's own worst relative error (over the three sizes' non-identical pairs, d and
 every d_k) from the float64 result; that single sample is close to rounding noise, hence the factor.  So that the rule cannot hide a
 failure the float32 oracle must itself lie within 1e-5 relative of float64 on every one of them.  Agreement with the lpips package
-on its released weights is not checked here: neither is available offline."""
+on its released weights is not checked here: neither is available offline.
+
+The pairs go through the workspace in groups whose size follows from the deepest feature map (plan() below restates the library's
+arithmetic): 8 at SIZES, and 7, 2 and 1 at GROUP_SIZES, the smallest near-square, non-square frames with those groups (800 x 800 and
+1008 x 756 have 2, LLFF's 504 x 378 has 7, everything from 1039 x 1039 up has 1).  Those are held to the same rule, with the limit
+from their own float32 oracle; stacks longer than a group and no multiple of it must give every pair the bits it has alone, in
+either order of the two stacks, through a NaN-filled workspace of exactly the reported size.  A NaN pixel makes its own pair's d and
+every d_k NaN, as it does the oracle's (F.relu passes a NaN on; so must the layer kernel's ReLU), and leaves the other pairs of its
+group their bits."""
 import json
 import os
 import re
@@ -24,7 +32,11 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = ((31, 31), (37, 50), (131, 97))          # the minimum (7, 3, 1, 1, 1); non-square, edge pixels dropped; row tiles and two-level sums
-FEATURE_MAPS = {(31, 31): ((7, 7), (3, 3), (1, 1)), (37, 50): ((8, 11), (3, 5), (1, 2)), (131, 97): ((32, 23), (15, 11), (7, 5))}
+GROUP_SIZES = {(411, 415): (7, 9), (747, 751): (2, 5), (1039, 1043): (1, 3)}      # pairs per group, and a stack longer than one and no multiple of it
+FEATURE_MAPS = {(31, 31): ((7, 7), (3, 3), (1, 1)), (37, 50): ((8, 11), (3, 5), (1, 2)), (131, 97): ((32, 23), (15, 11), (7, 5)),
+                (411, 415): ((102, 103), (50, 51), (24, 25)), (747, 751): ((186, 187), (92, 93), (45, 46)),
+                (1039, 1043): ((259, 260), (129, 129), (64, 64))}
+R2L_EINVAL = -1
 N, IDENTICAL = 3, 1
 CONVS = ((64, 3, 11, 4, 2), (192, 64, 5, 1, 2), (384, 192, 3, 1, 1), (256, 384, 3, 1, 1), (256, 256, 3, 1, 1))      # out, in, k, stride, pad
 SHIFT, SCALE = (-.030, -.088, -.188), (.458, .448, .450)
@@ -71,6 +83,24 @@ def oracle(weights, a, b, dtype):
     return layers.sum(1).double(), layers.double()
 
 
+def plan(H, W):
+    """csrc/r2l_lpips.hip's lpips_plan restated: (pairs per group, workspace floats).  Per image of a group the five feature maps,
+    the two pooled maps and the largest patch matrix; per pair conv 1's partial sums and 8 floats of d_k"""
+    conv = lambda v, k: (v + 2 * CONVS[k][4] - CONVS[k][2]) // CONVS[k][3] + 1
+    pool = lambda v: (v - 3) // 2 + 1
+    h, w, ins, outs = H, W, [], []
+    for k in range(5):
+        if k in (1, 2):
+            h, w = pool(h), pool(w)
+        ins.append(h * w)
+        h, w = conv(h, k), conv(w, k)
+        outs.append(h * w)
+    group = min(8, max(1, -(-4096 // outs[4])))
+    per_image = sum(outs[k] * CONVS[k][0] for k in range(5)) + ins[1] * CONVS[0][0] + ins[2] * CONVS[1][0] + \
+        max(outs[k] * CONVS[k][1] * CONVS[k][2] ** 2 for k in range(5))
+    return group, 2 * group * per_image + group * (-(-outs[0] // 32)) + group * 8
+
+
 def rel(got, want):
     """the worst relative error of d and of every d_k over the non-identical pairs; entries whose exact value is 0 must be 0"""
     worst = 0.
@@ -94,6 +124,22 @@ def cases(weights):
     out, worst = {}, 0.
     for j, (H, W) in enumerate(SIZES):
         a, b = frames(H, W, seed=10 + j)
+        want, own = oracle(weights, a, b, torch.float64), oracle(weights, a, b, torch.float32)
+        err = rel(own, want)
+        assert err <= 1e-5, f'{H} x {W}: the float32 oracle is {err:.2e} from float64: pick other seeds'
+        assert all(0.05 < float(want[0][k]) < 1. for k in range(N) if k != IDENTICAL) and float(want[0][IDENTICAL]) == 0.
+        out[(H, W)] = dict(a=a, b=b, want=want, oracle_err=err)
+        worst = max(worst, err)
+    out['oracle_err'], out['limit'] = worst, 8 * worst
+    return out
+
+
+@pytest.fixture(scope='module')
+def group_cases(weights):
+    """the same per size of GROUP_SIZES, with a limit of their own"""
+    out, worst = {}, 0.
+    for j, (H, W) in enumerate(GROUP_SIZES):
+        a, b = frames(H, W, seed=20 + j)
         want, own = oracle(weights, a, b, torch.float64), oracle(weights, a, b, torch.float32)
         err = rel(own, want)
         assert err <= 1e-5, f'{H} x {W}: the float32 oracle is {err:.2e} from float64: pick other seeds'
@@ -159,6 +205,99 @@ def test_symmetric_repeatable_and_independent_of_the_stack(pkg, built_lib, metri
     pick = [k % N for k in range(10)]
     mean_10, layers_10 = metric(a[pick].contiguous(), b[pick].contiguous(), return_layers=True)
     assert torch.equal(metric.last_d, d[pick]) and torch.equal(layers_10, layers[pick]) and mean_10 == float(d[pick].double().mean())
+
+
+@pytest.mark.parametrize('size', list(GROUP_SIZES))
+def test_parity_at_groups_of_7_2_and_1(pkg, built_lib, metric, group_cases, size):
+    """the same rule where the workspace holds 7, 2 and 1 pairs at a time; the reported workspace is the plan's, so the group is"""
+    from efficient_nerf_amd import _lib
+    c = group_cases[size]
+    H, W = size
+    sizes = FEATURE_MAPS[size]
+    group, floats = plan(H, W)
+    need = _lib.lib().r2l_lpips_workspace_floats(H, W)
+    p1, p2, p3 = (h * w for h, w in sizes)
+    assert group == GROUP_SIZES[size][0] and min(8, -(-4096 // p3)) == group
+    assert need >= group * (2 * p1 * (363 + 64) + 2 * p2 * 192 + 2 * p3 * (384 + 256 + 256)) and need == floats
+    mean, d, layers = run(metric, c['a'], c['b'])
+    err = rel((d, layers), c['want'])
+    print(f'{H} x {W} (feature maps {sizes}, {group} pairs a group): float32 oracle {c["oracle_err"]:.3e} (worst of the sizes '
+          f'{group_cases["oracle_err"]:.3e}), HIP {err:.3e}, limit {group_cases["limit"]:.3e}, HIP / limit {err / group_cases["limit"]:.3f}; '
+          f'd = {[round(float(v), 6) for v in d]}')
+    assert torch.isfinite(d).all() and torch.isfinite(layers).all()
+    assert float(d[IDENTICAL]) == 0. and torch.all(layers[IDENTICAL] == 0.)
+    assert err <= group_cases['limit']
+    assert mean == float(d.double().mean())
+
+
+def bits(t):
+    return t.contiguous().view(torch.int32)
+
+
+def raw_call(metric, a, b, floats):
+    """one r2l_lpips call through a NaN-filled workspace of `floats` floats: (return code, d, layers), d and layers pre-filled with -1"""
+    from efficient_nerf_amd import _lib
+    n, H, W = a.shape[:3]
+    ws = torch.full((floats,), float('nan'), device='cuda')
+    d, layers = torch.full((n,), -1., device='cuda'), torch.full((n, 5), -1., device='cuda')
+    rc = _lib.lib().r2l_lpips(metric._ctx, _lib.dptr(a), _lib.dptr(b), n, H, W, 0., 1., 0., 0., 1., 0., _lib.dptr(d), _lib.dptr(layers), _lib.dptr(ws),
+                              floats, _lib.current_stream())
+    torch.cuda.synchronize()
+    return rc, d, layers
+
+
+@pytest.mark.parametrize('size', list(GROUP_SIZES))
+def test_a_pair_does_not_depend_on_its_group_below_8(pkg, built_lib, metric, group_cases, size):
+    """a stack of more than one group and no multiple of it: every pair has the bits it has alone, d(a, b) = d(b, a); a NaN-filled
+    workspace of exactly the reported size gives the same bits, one float less is refused before any launch"""
+    from efficient_nerf_amd import _lib
+    group, n_stack = GROUP_SIZES[size]
+    assert n_stack > group and (n_stack % group or group == 1) and plan(*size)[0] == group
+    a, b = group_cases[size]['a'].cuda(), group_cases[size]['b'].cuda()
+    alone = [run(metric, a[k:k + 1], b[k:k + 1]) for k in range(N)]
+    d = torch.cat([one[1] for one in alone])
+    layers = torch.cat([one[2] for one in alone])
+    pick = [k % N for k in range(n_stack)]
+    sa, sb = a[pick].contiguous(), b[pick].contiguous()
+    mean, d_stack, layers_stack = run(metric, sa, sb)
+    assert torch.equal(d_stack, d[pick]) and torch.equal(layers_stack, layers[pick]) and mean == float(d[pick].double().mean())
+    _, d_ba, layers_ba = run(metric, sb, sa)
+    assert torch.equal(d_ba, d_stack) and torch.equal(layers_ba, layers_stack)
+    need = _lib.lib().r2l_lpips_workspace_floats(*size)
+    rc, d_raw, layers_raw = raw_call(metric, sa, sb, need)
+    assert rc == 0 and torch.equal(bits(d_raw), bits(d_stack)) and torch.equal(bits(layers_raw), bits(layers_stack))
+    rc, d_raw, layers_raw = raw_call(metric, sa, sb, need - 1)
+    assert rc == R2L_EINVAL and 'workspace' in _lib.lib().r2l_last_error().decode()
+    assert torch.all(d_raw == -1.) and torch.all(layers_raw == -1.)          # nothing was launched
+
+
+def _nan_checks(metric, weights, a, b, pick, at):
+    """stacks a[pick], b[pick] with a NaN at a_stack[at]: that pair's d and d_k are NaN as the float64 oracle's are, every other pair
+    keeps the bits it has without the NaN"""
+    sa, sb = a[pick].contiguous().cuda(), b[pick].contiguous().cuda()
+    _, d, layers = run(metric, sa, sb)
+    assert torch.isfinite(d).all() and torch.isfinite(layers).all()
+    sa[at] = float('nan')
+    k = at[0]
+    want_d, want_layers = oracle(weights, sa[k:k + 1].cpu(), sb[k:k + 1].cpu(), torch.float64)
+    assert torch.isnan(want_d).all() and torch.isnan(want_layers).all()
+    mean, d_nan, layers_nan = run(metric, sa, sb)
+    others = [j for j in range(len(pick)) if j != k]
+    print(f'{tuple(sa.shape)} with a NaN at {at}: d = {[float(v) for v in d_nan]}, d_k of that pair = {[float(v) for v in layers_nan[k]]}')
+    assert torch.isnan(d_nan[k]) and torch.isnan(layers_nan[k]).all() and np.isnan(mean)
+    assert torch.equal(bits(d_nan[others]), bits(d[others])) and torch.equal(bits(layers_nan[others]), bits(layers[others]))
+    _, d_ba, layers_ba = run(metric, sb, sa)
+    assert torch.isnan(d_ba[k]) and torch.isnan(layers_ba[k]).all() and torch.equal(bits(d_ba[others]), bits(d[others]))
+
+
+def test_a_nan_pixel_makes_its_pair_nan_and_no_other(pkg, built_lib, metric, weights, cases, group_cases):
+    """37 x 50, a[0, 5, 7, 1] = NaN; 411 x 415, the NaN in the last pair of 9 (a group of 7 and one of 2)"""
+    size = SIZES[1]
+    _nan_checks(metric, weights, cases[size]['a'], cases[size]['b'], list(range(N)), (0, 5, 7, 1))
+    size = (411, 415)
+    n_stack = GROUP_SIZES[size][1]
+    _nan_checks(metric, weights, group_cases[size]['a'], group_cases[size]['b'], [k % N for k in range(n_stack)], (n_stack - 1, 200, 300, 1))
+    _nan_checks(metric, weights, group_cases[size]['a'], group_cases[size]['b'], [k % N for k in range(n_stack)], (3, 0, 0, 2))
 
 
 def test_a_dead_layer_gives_zero_not_nan(pkg, built_lib, weights, cases):
