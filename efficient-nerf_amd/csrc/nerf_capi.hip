@@ -978,3 +978,13 @@ int nerf_merge_sorted(const float* a, int na, const float* b, int nb, int n, flo
     HIPCHK(nerf_launch_merge(a, na, na, b, nb, n, out, (hipStream_t)stream), "merge");
     return R2L_OK;
 }
+
+int nerf_sort_rows(const float* x, int n, int N, float* out, void* stream) {
+    if (!x || !out || n < 0 || N < 1 || N > 256)
+        return r2l_set_error(R2L_EINVAL, "bad argument to nerf_sort_rows (the row length must be 1..256)");
+    int rc = r2l_require_gfx950(nullptr);
+    if (rc) return rc;
+    if (n == 0) return R2L_OK;
+    HIPCHK(nerf_launch_sort_rows(x, n, N, out, (hipStream_t)stream), "sort_rows");
+    return R2L_OK;
+}

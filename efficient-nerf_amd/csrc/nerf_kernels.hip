@@ -666,7 +666,8 @@ __global__ __launch_bounds__(256) void nerf_raw2outputs_kernel(const float* __re
         dist = dist * norm;
         const f32x4 r4 = *reinterpret_cast<const f32x4*>(raw + ((size_t)ray * S + ii) * 4);
         // raw2alpha(raw[..., 3] + noise, dists), noise = randn * raw_noise_std drawn by the caller (main.py:592-600)
-        const float sig = fmaxf(noise ? r4[3] + noise[(size_t)ray * S + ii] : r4[3], 0.0f);  // F.relu
+        const float pre = noise ? r4[3] + noise[(size_t)ray * S + ii] : r4[3];
+        const float sig = (pre != pre) ? pre : fmaxf(pre, 0.0f);  // F.relu: a NaN stays a NaN (fmaxf alone returns the 0)
         float a = 1.0f - expf(-sig * dist);                   // 1 - exp(-relu(raw) * dists)
         if (!ok) a = 0.0f;
         alpha[c] = a;
@@ -795,10 +796,10 @@ __global__ __launch_bounds__(256) void nerf_sample_pdf_kernel(const float* __res
         float u;
         if (u_arr) u = u_arr[(size_t)ray * u_stride + k];
         else u = (k < N / 2 || N == 1) ? __fmul_rn(step, (float)k) : __fsub_rn(1.0f, __fmul_rn(step, (float)(N - k - 1)));
-        int lo = 0, hi = n_bins;  // searchsorted(cdf, u, right=True): first index with cdf > u
+        int lo = 0, hi = n_bins;  // searchsorted(cdf, u, right=True) as ATen writes it, !(cdf[mid] > u): a NaN on either side goes right
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
-            if (s_cdf[wv][mid] <= u) lo = mid + 1; else hi = mid;
+            if (!(s_cdf[wv][mid] > u)) lo = mid + 1; else hi = mid;
         }
         if (inds_out) inds_out[(size_t)ray * N + k] = lo;
         const int below = lo - 1 > 0 ? lo - 1 : 0;
@@ -812,6 +813,11 @@ __global__ __launch_bounds__(256) void nerf_sample_pdf_kernel(const float* __res
     }
 }
 
+// torch.sort's order of floats: ascending, every NaN behind every number (+inf included), NaNs equal among themselves; -0 == 0.
+// A total preorder, which the bitonic network and the rank searches of the merge need: with a plain < every comparison against
+// a NaN is false, the network no longer sorts the numbers and two ranks of the merge coincide (a slot stays unwritten).
+__device__ __forceinline__ bool nerf_before(float a, float b) { return a < b || (a == a && b != b); }
+
 // rows of N <= 256 floats sorted ascending (bitonic network in LDS, one wave per row): with random uniforms
 // (perturb > 0) sample_pdf's output is not monotone and the reference's sort (main.py:730-732) is a real sort
 __global__ __launch_bounds__(256) void nerf_sort_rows_kernel(const float* __restrict__ x, int n, int N, float* __restrict__ out) {
@@ -820,7 +826,7 @@ __global__ __launch_bounds__(256) void nerf_sort_rows_kernel(const float* __rest
     const int ray = blockIdx.x * 4 + wv;
     const int lane = threadIdx.x & 63;
     if (ray >= n) return;
-    for (int i = lane; i < 256; i += 64) s[wv][i] = i < N ? x[(size_t)ray * N + i] : __builtin_huge_valf();
+    for (int i = lane; i < 256; i += 64) s[wv][i] = i < N ? x[(size_t)ray * N + i] : __builtin_nanf("");  // the padding sorts last
     for (int k = 2; k <= 256; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
             __builtin_amdgcn_wave_barrier();
@@ -830,7 +836,7 @@ __global__ __launch_bounds__(256) void nerf_sort_rows_kernel(const float* __rest
                 if (p > i) {
                     const float a = s[wv][i], b = s[wv][p];
                     const bool up = (i & k) == 0;
-                    if ((a > b) == up) {
+                    if (nerf_before(b, a) == up) {
                         s[wv][i] = b;
                         s[wv][p] = a;
                     }
@@ -876,21 +882,21 @@ __global__ __launch_bounds__(256) void nerf_merge_kernel(const float* __restrict
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     float* o = out + (size_t)ray * (na + nb);
-    for (int i = lane; i < na; i += 64) {  // rank of a[i] = i + #{b < a[i]}
+    for (int i = lane; i < na; i += 64) {  // rank of a[i] = i + #{b before a[i]}
         const float v = s_a[wv][i];
         int lo = 0, hi = nb;
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
-            if (s_b[wv][mid] < v) lo = mid + 1; else hi = mid;
+            if (nerf_before(s_b[wv][mid], v)) lo = mid + 1; else hi = mid;
         }
         o[i + lo] = v;
     }
-    for (int j = lane; j < nb; j += 64) {  // rank of b[j] = j + #{a <= b[j]}
+    for (int j = lane; j < nb; j += 64) {  // rank of b[j] = j + #{a not behind b[j]}: on a tie a's element first, as a stable sort of cat(a, b)
         const float v = s_b[wv][j];
         int lo = 0, hi = na;
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
-            if (s_a[wv][mid] <= v) lo = mid + 1; else hi = mid;
+            if (!nerf_before(v, s_a[wv][mid])) lo = mid + 1; else hi = mid;
         }
         o[j + lo] = v;
     }
@@ -931,7 +937,8 @@ __global__ __launch_bounds__(256) void nerf_coarse_scan_kernel(const float* __re
     float dist = (ii < S - 1) ? (zn - zc) : 1e10f;
     dist = dist * norm;
     const f32x4 r4 = *reinterpret_cast<const f32x4*>(raw + ((size_t)ray * S + ii) * 4);
-    const float sig = fmaxf(noise ? r4[3] + noise[(size_t)ray * S + ii] : r4[3], 0.0f);
+    const float pre = noise ? r4[3] + noise[(size_t)ray * S + ii] : r4[3];
+    const float sig = (pre != pre) ? pre : fmaxf(pre, 0.0f);
     float a = 1.0f - expf(-sig * dist);
     if (!ok) a = 0.0f;
     const float cr = 1.0f / (1.0f + expf(-r4[0])), cg = 1.0f / (1.0f + expf(-r4[1])), cb = 1.0f / (1.0f + expf(-r4[2]));
@@ -1000,7 +1007,7 @@ __global__ __launch_bounds__(256) void nerf_coarse_scan_kernel(const float* __re
         int lo = 0, hi = n_bins;
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
-            if (s_cdf[wv][mid] <= u) lo = mid + 1; else hi = mid;
+            if (!(s_cdf[wv][mid] > u)) lo = mid + 1; else hi = mid;
         }
         const int below = lo - 1 > 0 ? lo - 1 : 0;
         const int above = lo < n_bins - 1 ? lo : n_bins - 1;
@@ -1022,7 +1029,7 @@ __global__ __launch_bounds__(256) void nerf_coarse_scan_kernel(const float* __re
         int lo = 0, hi = N;
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
-            if (s_s[wv][mid] < v) lo = mid + 1; else hi = mid;
+            if (nerf_before(s_s[wv][mid], v)) lo = mid + 1; else hi = mid;
         }
         o[lane + lo] = v;
     }
@@ -1031,7 +1038,7 @@ __global__ __launch_bounds__(256) void nerf_coarse_scan_kernel(const float* __re
         int lo = 0, hi = S;
         while (lo < hi) {
             const int mid = (lo + hi) >> 1;
-            if (s_z[wv][mid] <= v) lo = mid + 1; else hi = mid;
+            if (!nerf_before(v, s_z[wv][mid])) lo = mid + 1; else hi = mid;
         }
         o[j + lo] = v;
     }

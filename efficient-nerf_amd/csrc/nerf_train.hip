@@ -49,17 +49,19 @@ __device__ __forceinline__ double nt_shfl_f64(double v, int src) {
 // alpha and dist * exp(-s dist) of sample i (i < S) as the forward kernel computes alpha
 struct NtSample {
     float alpha, dalpha;   // dalpha = d alpha / d raw_sigma (0 where the relu is closed)
+    bool closed;           // raw_sigma + noise <= 0 (false for a NaN)
 };
 __device__ __forceinline__ NtSample nt_sample(const float* __restrict__ zr, const float* __restrict__ noise_r, float raw_sigma, int i,
                                               int S, float norm) {
     float dist = (i < S - 1) ? (zr[i + 1] - zr[i]) : 1e10f;   // dists = cat(z[1:] - z[:-1], 1e10)
     dist = dist * norm;
     const float pre = noise_r ? raw_sigma + noise_r[i] : raw_sigma;
-    const float sig = fmaxf(pre, 0.0f);
+    const float sig = (pre != pre) ? pre : fmaxf(pre, 0.0f);  // F.relu: a NaN stays a NaN (fmaxf alone returns the 0)
     const float e = expf(-sig * dist);
     NtSample o;
     o.alpha = 1.0f - e;
-    o.dalpha = pre > 0.0f ? dist * e : 0.0f;
+    o.closed = pre <= 0.0f;                                   // threshold_backward: 0 where x <= 0, the gradient elsewhere (NaN included)
+    o.dalpha = o.closed ? 0.0f : dist * e;                    // NaN where pre is
     return o;
 }
 
@@ -108,7 +110,7 @@ __global__ __launch_bounds__(256) void nerf_raw2outputs_backward_kernel(const fl
         const int i = k * 64 + lane;
         const bool ok = i < S;
         f32x4 r4 = {0.f, 0.f, 0.f, 0.f};
-        NtSample sm = {0.f, 0.f};
+        NtSample sm = {0.f, 0.f, true};
         float T = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, q = 0.f;
         double a = 0.0, p = 1.0;               // the identity map on the lanes behind the ray's end
         if (ok) {
@@ -141,7 +143,10 @@ __global__ __launch_bounds__(256) void nerf_raw2outputs_backward_kernel(const fl
             o[0] = (w * g0) * (c0 * (1.0f - c0));
             o[1] = (w * g1) * (c1 * (1.0f - c1));
             o[2] = (w * g2) * (c2 * (1.0f - c2));
-            o[3] = sm.dalpha == 0.0f ? 0.0f : g_alpha * sm.dalpha;
+            // a closed relu gives 0 whatever arrives; an open one with dist exp(-s dist) = 0 gives 0 (not -0) to a finite g_alpha and,
+            // as autograd's product, NaN to a NaN or infinite one
+            const float g_s = g_alpha * sm.dalpha;
+            o[3] = (sm.closed || (sm.dalpha == 0.0f && g_s == g_s)) ? 0.0f : g_s;
             *reinterpret_cast<f32x4*>(gr + (size_t)i * 4) = o;
         }
     }

@@ -4,6 +4,7 @@
 //
 // A layer computes y = post + act(u), u = s (x W^T + b) + res.  Given g_y:
 //   r2l_train_act_backward   g_post (+)= g_y;  g_u = g_y * act'(a), a = y - post;  g_res (+)= g_u;  g_z = s g_u
+//                            (ReLU selects as torch's threshold_backward: 0 where a <= 0 whatever g_y holds, g_y elsewhere, at a NaN too)
 //   r2l_train_grad_input     g_x [n, in] (+)= g_z [n, out] W [out, in]
 //   r2l_train_grad_weight    g_W [out, in] = g_z^T x,  g_b = sum over rays of g_z
 // Both GEMMs run on v_mfma_f32_32x32x2_f32 like the forward kernel (fp32 products, fp32 accumulation in k order).  g_W reduces over
@@ -36,7 +37,6 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 __device__ __forceinline__ float r2l_act_grad(float a, int act) {
     switch (act) {
-        case R2L_ACT_RELU: return a > 0.0f ? 1.0f : 0.0f;
         case R2L_ACT_LRELU: return a > 0.0f ? 1.0f : 0.01f;
         case R2L_ACT_SIGMOID: return a * (1.0f - a);
         default: return 1.0f;
@@ -54,7 +54,8 @@ __global__ void r2l_act_backward_kernel(const float* g_y, long long ldg, const f
     const float gy = g_y[r * ldg + c];
     float a = y[r * ldy + c];
     if (post) a = a - post[r * ldp + c];
-    const float gu = gy * r2l_act_grad(a, act);
+    // ReLU selects as torch's threshold_backward does (0 at a closed unit whatever g_y holds, g_y itself elsewhere); the others multiply
+    const float gu = act == R2L_ACT_RELU ? (a <= 0.0f ? 0.0f : gy) : gy * r2l_act_grad(a, act);
     // g_post first: g_res may be the same buffer (a one-block body under --use_residual), and then holds g_y + g_u
     if (g_post) g_post[r * ldq + c] = post_acc ? g_post[r * ldq + c] + gy : gy;
     if (g_res) g_res[r * ldr + c] = res_acc ? g_res[r * ldr + c] + gu : gu;
@@ -270,7 +271,12 @@ __global__ void r2l_adam_kernel(float* __restrict__ p, const float* __restrict__
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     const float gi = g[i];
-    const float mi = m[i] * b1 + one_b1 * gi;
+    const float m0 = m[i], dm = gi - m0;
+    // torch steps exp_avg by lerp_(g, 1 - b1) = m + (1 - b1) (g - m).  Where g - m is not a number that form and the two products
+    // part: inf - inf is NaN (an infinite gradient on an infinite moment of its sign), a finite gradient on an infinite moment
+    // gives inf + -inf = NaN, a difference that overflows gives inf.  There the kernel takes lerp's form; a finite g - m keeps the
+    // products', as before.
+    const float mi = (fabsf(dm) <= 3.402823466e+38f) ? m0 * b1 + one_b1 * gi : m0 + one_b1 * dm;
     const float vi = v[i] * b2 + (one_b2 * gi) * gi;
     m[i] = mi;
     v[i] = vi;

@@ -430,9 +430,12 @@ int nerf_sample_pdf_u(const float* bins, const float* weights, int n, int n_bins
 int nerf_sample_pdf_ex(const float* bins, const float* weights, int n, int n_bins, const float* u_dev,
                        int u_per_ray, int N, float* samples, float* cdf_out_dev, int* inds_out_dev,
                        void* stream);
-/* a [n,na] and b [n,nb], each row ascending -> out [n,na+nb] ascending */
+/* a [n,na] and b [n,nb], each row ascending -> out [n,na+nb] ascending, = torch.sort(cat(a, b), stable): every NaN behind every
+ * number (a row's NaNs trail it), a's element first on a tie; every slot of out is written */
 int nerf_merge_sorted(const float* a, int na, const float* b, int nb, int n, float* out,
                       void* stream);
+/* x [n,N] -> out [n,N], every row ascending as torch.sort orders floats (-inf ... +inf, then the NaNs); N <= 256 */
+int nerf_sort_rows(const float* x, int n, int N, float* out, void* stream);
 
 /* ---- generic fp32 layer path (csrc/r2l_generic.hip) ---------------------------------------------------------------
  * The variants the reference's constructors accept that the fused kernels are not built for: NeRF_v3_2 with netwidth != 256,

@@ -18,7 +18,7 @@ def test_header_declares_expected_entry_points():
     names = declared_symbols()
     for must in ['r2l_create', 'r2l_load_weights', 'r2l_render', 'r2l_render_rays', 'r2l_destroy',
                  'r2l_sample_embed', 'nerf_create', 'nerf_load_weights', 'nerf_render', 'nerf_raw2outputs',
-                 'nerf_sample_pdf', 'nerf_merge_sorted']:
+                 'nerf_sample_pdf', 'nerf_merge_sorted', 'nerf_sort_rows']:
         assert must in names
 
 

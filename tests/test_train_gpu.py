@@ -302,6 +302,40 @@ def test_whole_network_gradients_small_variants(pkg):
     _band_check('small variants', hip, t32, losses)
 
 
+def test_one_step_with_a_nan_ray(pkg):
+    """257 rays through the smallest network above (4 layers of 32, one block), ray 100's origin NaN -- the row r2l_rays_from_images
+    writes for an index outside the images: the loss is NaN, as float32 autograd's, and every gradient tensor has float32
+    autograd's NaN and infinity masks (float64's are the same); the per-ray error is NaN on that ray alone"""
+    from efficient_nerf_amd.train import R2LTrainer
+    from oracle import r2l_oracle as O
+    n, n_sample, Lf, bad = 257, 4, 3, 100
+    D, W, lw, act, use_res, trial = SMALL[4]
+    tr = R2LTrainer(n_sample=n_sample, L=Lf, netdepth=D, netwidth=W, layerwise_netwidths=lw, act=act, use_residual=use_res, trial=trial,
+                    max_rays=n)
+    sd = O.make_v3_2_state(4, D, W, tr.input_dim, lw, act, trial)
+    tr.load_state_dict(sd)
+    g = torch.Generator().manual_seed(204)
+    ro, rd, _ = _rays(n, 54)
+    ro[bad] = float('nan')
+    target, t_rand = torch.rand(n, 3, generator=g), torch.rand(n, n_sample, generator=g)
+    emb = tr.embed(ro.cuda(), rd.cuda(), 1., t_rand.cuda()).cpu()
+    assert torch.isnan(emb[bad]).any() and torch.isfinite(emb[[r for r in range(n) if r != bad]]).all()
+    loss = tr.forward_backward(ro.cuda(), rd.cuda(), target.cuda(), 1., t_rand.cuda()).item()
+    fwd = lambda prm, x: O.v3_2_forward(prm, x, D, act, use_res, trial)
+    l32, g32 = _autograd(fwd, sd, emb, target, torch.float32)
+    l64, g64 = _autograd(fwd, sd, emb, target, torch.float64)
+    masks = lambda t: (torch.isnan(t), t == float('inf'), t == -float('inf'))
+    got = tr.grads()
+    assert np.isnan(l32) and np.isnan(l64) and np.isnan(loss)
+    assert set(got) == set(g32)
+    for k in g32:
+        assert all(torch.equal(a, b) for a, b in zip(masks(g32[k]), masks(g64[k].float()))), k      # the precondition
+        assert all(torch.equal(a, b) for a, b in zip(masks(got[k].cpu()), masks(g32[k]))), k
+    assert any(torch.isnan(v).any() for v in g32.values())
+    err = tr._err[:n].cpu()
+    assert torch.isnan(err[bad]) and torch.isfinite(err[[r for r in range(n) if r != bad]]).all()
+
+
 # ---- 4. jitter ---------------------------------------------------------------------------------------------------------------
 def test_sample_train_jitter_bit_equal(pkg):
     from efficient_nerf_amd import PointSampler
