@@ -609,7 +609,8 @@ static int ensure_alpha_img(nerf_ctx* c) {
 }
 
 static int run_mlp(nerf_ctx* c, int which, const float* rays_o, const float* rays_d, const float* z, int z_stride,
-                   int S, int n, float* raw, hipStream_t s, const float* viewdirs = nullptr, bool alpha_only = false, bool second_exit = false) {
+                   int S, int n, float* raw, hipStream_t s, const float* viewdirs = nullptr, bool alpha_only = false, bool second_exit = false,
+                   bool ordered_rows = false) {
     NerfMlpParams p;
     memset(&p, 0, sizeof p);
     p.viewdirs = viewdirs;
@@ -667,6 +668,9 @@ static int run_mlp(nerf_ctx* c, int which, const float* rays_o, const float* ray
     hipError_t e = nerf_launch_mlp(p, mode, grid, s, x1_nc, stream_embed, alpha_only, second_exit);
     if (c->timing) (void)hipEventRecord(e1, s);
     if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "nerf_mlp launch: %s", hipGetErrorString(e));
+    // a point or a direction with a NaN in its embedding: NaN into its raw, as the reference's networks give (the kernels' ReLU dropped it)
+    e = nerf_launch_mark_nonfinite(p, ordered_rows, s);
+    if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "nerf non-finite ray pass: %s", hipGetErrorString(e));
     return R2L_OK;
 }
 
@@ -725,7 +729,12 @@ static int render_rays_dev(nerf_ctx* c, const float* rays_o, const float* rays_d
     const float* zc = o.z_coarse ? o.z_coarse : c->d_zc;
     const int zc_stride = o.z_coarse ? S0 : 0;
     // coarse network_fn; with nerf_set_skip_rgb0 without its view branch: raw0 = (0, 0, 0, sigma), sigma bit for bit the full chain's
-    int rc = run_mlp(c, 0, rays_o, rays_d, zc, zc_stride, S0, n, c->d_raw0, s, vd, c->skip_rgb0);
+    // non-finite points (run_mlp's marking pass): the engine's own coarse depths and uniforms in ascending order make every row of both
+    // passes ascending with its NaNs last, and the first and the last depth decide a ray; a caller's rows are taken sample by sample
+    bool ordered = !o.z_coarse;
+    for (int i = 0; ordered && i < S0; ++i) ordered = fabsf(c->z_coarse[i]) <= 3.4028235e38f && (i == 0 || c->z_coarse[i - 1] <= c->z_coarse[i]);
+    for (int i = 0; ordered && !o.u && i < NI; ++i) ordered = fabsf(c->u[i]) <= 3.4028235e38f && (i == 0 || c->u[i - 1] <= c->u[i]);
+    int rc = run_mlp(c, 0, rays_o, rays_d, zc, zc_stride, S0, n, c->d_raw0, s, vd, c->skip_rgb0, false, ordered);
     if (rc) return rc;
     if (!o.u && !c->split_scans) {
         // deterministic test path: raw2outputs(coarse) + sample_pdf + merge as ONE launch (nerf_coarse_scan_kernel: the weights,
@@ -753,7 +762,7 @@ static int render_rays_dev(nerf_ctx* c, const float* rays_o, const float* rays_d
     }
     // network_fine; with nerf_set_skip_rgb0 and no density noise on the chain with the second exit: the colours of workgroup tiles without a
     // positive density (weight 0 exactly) are not computed -- raw shows zeros there, every map is bit for bit the same
-    rc = run_mlp(c, 1, rays_o, rays_d, c->d_zall, S1, S1, n, c->d_raw, s, vd, false, c->skip_rgb0 && !o.noise1);
+    rc = run_mlp(c, 1, rays_o, rays_d, c->d_zall, S1, S1, n, c->d_raw, s, vd, false, c->skip_rgb0 && !o.noise1, ordered);
     if (rc) return rc;
     HIPCHK(nerf_launch_raw2outputs(c->d_raw, c->d_zall, S1, rays_d, n, S1, c->white_bkgd, rgb, disp, acc, nullptr,
                                    depth, s, o.noise1), "raw2outputs(fine)");

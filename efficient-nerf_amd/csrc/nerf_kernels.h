@@ -29,6 +29,10 @@ struct NerfMlpParams {
 hipError_t nerf_launch_mlp(const NerfMlpParams& p, int mode, int grid, hipStream_t stream, int x1_col_tiles = 2, bool stream_embed = false,
                            bool alpha_only = false, bool second_exit = false);
 
+// behind nerf_launch_mlp: NaN into p.raw of every sample whose point embedding, and of every ray whose view-direction embedding,
+// holds a NaN; ordered_rows: every row of p.z is ascending with its NaNs last (first and last depth decide a ray)
+hipError_t nerf_launch_mark_nonfinite(const NerfMlpParams& p, bool ordered_rows, hipStream_t stream);
+
 // rays of rows [row_begin,row_end) of one frame (utils/run_nerf_raybased_helpers.py:231-257)
 hipError_t nerf_launch_get_rays(const float* c2w12_host, int W, float half_w, float half_h, float focal,
                                 int pix_begin, int n, float* rays_o, float* rays_d, hipStream_t stream);

@@ -535,6 +535,53 @@ __global__ __launch_bounds__(256, 1) void nerf_chain_emb_kernel(NerfMlpParams p)
 }
 
 // ====================================================================================
+// non-finite points and directions.  The reference's networks give NaN where an embedding holds one -- relu keeps it
+// (torch) --, the MLP kernels' ReLU (fmaxf, v_max in the generated chains) drops it.  What the embeddings hold depends on the ray and
+// the depth alone, so one thread per ray behind every MLP launch restates nerf_tile_embed's points and view direction and writes into
+// `raw`, which the scan kernels carry on as torch does:
+//   a sample's point is NaN, infinite or overflows under 2^9  -> all four channels of that sample NaN;
+//   the ray's view direction is NaN or infinite (rays_d = 0: 0 / 0)  -> the three colours of every sample NaN, the densities stand.
+// ordered_rows: the caller knows every row of z to be ascending with its NaNs last (a render on the engine's own coarse depths and
+// uniforms, both passes): the points are monotone in the depth, so a ray whose first and last point embed to numbers has no other and costs
+// 24 B + two depths; any other ray, and every ray of a row in the caller's own order, is decided sample by sample.
+// ====================================================================================
+__global__ void nerf_mark_nonfinite_kernel(NerfMlpParams p, int ordered_rows) {
+    const int ray = blockIdx.x * blockDim.x + threadIdx.x;
+    if (ray >= p.n_rays) return;
+    float o[3], d[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        o[k] = p.rays_o[(size_t)ray * 3 + k];
+        d[k] = p.rays_d[(size_t)ray * 3 + k];
+    }
+    const float nrm = sqrtf(__fadd_rn(__fadd_rn(d[0] * d[0], d[1] * d[1]), d[2] * d[2]));
+    bool dir = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) dir = dir && embed_arg_finite(p.viewdirs ? p.viewdirs[(size_t)ray * 3 + k] : __fdiv_rn(d[k], nrm), 8.0f);
+    auto point_ok = [&](float z) {
+        bool ok = true;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) ok = ok && embed_arg_finite(__fadd_rn(o[k], __fmul_rn(d[k], z)), 512.0f);
+        return ok;
+    };
+    const float* __restrict__ z = p.z + (size_t)ray * p.z_stride;
+    if (dir && ordered_rows && point_ok(z[0]) && point_ok(z[p.S - 1])) return;
+    const float nan = __builtin_nanf("");
+    float* __restrict__ out = p.raw + (size_t)ray * p.S * 4;
+    for (int s = 0; s < p.S; ++s) {
+        const bool pos = point_ok(z[s]);
+        if (pos && dir) continue;
+        out[4 * s] = out[4 * s + 1] = out[4 * s + 2] = nan;
+        if (!pos) out[4 * s + 3] = nan;
+    }
+}
+
+hipError_t nerf_launch_mark_nonfinite(const NerfMlpParams& p, bool ordered_rows, hipStream_t stream) {
+    hipLaunchKernelGGL(nerf_mark_nonfinite_kernel, dim3((p.n_rays + 255) / 256), dim3(256), 0, stream, p, ordered_rows ? 1 : 0);
+    return hipGetLastError();
+}
+
+// ====================================================================================
 // get_rays
 // ====================================================================================
 __global__ void nerf_get_rays_kernel(float c00, float c01, float c02, float c03, float c10, float c11, float c12,

@@ -1206,7 +1206,33 @@ static int launch_split(r2l_ctx* c, const R2LParams& p, hipStream_t s) {
     return R2L_OK;
 }
 
+static int render_launch(r2l_ctx* c, const R2LParams& p, hipStream_t s);
+
+// Can a ray of this host pose have a non-finite embedding?  Twelve comparisons: no component of a camera ray's sample
+// exceeds max|c2w| (1 + ((W / 2 + H / 2) / |focal| + 1) max|z|), and the embedding scales it by 2^9.  A NaN or an infinity in the pose
+// fails the comparison.  A pose inside the bound -- every pose of a real path -- renders without the marking pass.
+static bool host_pose_finite(const r2l_ctx* c, const float* c2w) {
+    double amax = 0, zmax = 1;
+    for (int i = 0; i < 12; ++i) {
+        if (!(fabs((double)c2w[i]) <= 3.4028235e38)) return false;
+        amax = fmax(amax, fabs((double)c2w[i]));
+    }
+    for (int i = 0; i < R2L_NSAMPLE; ++i) zmax = fmax(zmax, fabs((double)c->z[i]));
+    const double dirs = ((double)c->W * .5 + (double)c->H * .5) / fabs(c->focal) + 1.0;
+    return amax * (1.0 + dirs * zmax) * 512.0 < 1e38;
+}
+
+// the render, then the marking pass over its rgb in stream order -- unless the rays come from a host pose that cannot need it
 static int timed_launch(r2l_ctx* c, const R2LParams& p, hipStream_t s) {
+    int rc = render_launch(c, p, s);
+    if (rc) return rc;
+    if (p.rays_o == nullptr && p.c2w == nullptr && host_pose_finite(c, p.c2w_host)) return R2L_OK;
+    hipError_t e = r2l_launch_mark_nonfinite(p, s);
+    if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "r2l non-finite ray pass: %s", hipGetErrorString(e));
+    return R2L_OK;
+}
+
+static int render_launch(r2l_ctx* c, const R2LParams& p, hipStream_t s) {
     if (split_mode(c->mode)) return launch_split(c, p, s);
     const int grid = balanced_grid(p.n_tiles, c->n_cu);
     hipEvent_t e0 = nullptr, e1 = nullptr;

@@ -52,6 +52,10 @@ __device__ __forceinline__ float trig_pow2(Rev r, float pow2l, bool is_cos) {
     return __builtin_amdgcn_sinf(arg);               // v_sin_f32 reduces |arg| <= 1/2 itself
 }
 
+// The reference takes sin / cos of the ROUNDED product x 2^l (model/nerf_raybased.py:198-208): where that product overflows it is
+// sin(inf), a NaN, while rh 2^l above stays finite for two more octaves.  A NaN or infinite x fails the comparison as well.
+__device__ __forceinline__ bool embed_arg_finite(float x, float pow2l) { return fabsf(__fmul_rn(x, pow2l)) <= 3.4028235e38f; }
+
 // ------------------------------------------------------------------------------------
 // LDS weight ring + MFMA k-step
 // ------------------------------------------------------------------------------------

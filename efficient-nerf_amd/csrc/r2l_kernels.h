@@ -71,5 +71,7 @@ int r2l_body_lds_bytes();
 int r2l_body_guard_max_blocks(int e4m3);   // largest n_block whose 2 n_block maxima rows fit the LDS beside the ring
 hipError_t r2l_launch_sample_embed(const R2LParams& p, float* pts_out, float* emb_out,
                                    hipStream_t stream);
+// behind the last launch of a render: NaN into p.rgb of every ray of the call whose embedding holds a NaN
+hipError_t r2l_launch_mark_nonfinite(const R2LParams& p, hipStream_t stream);
 hipError_t r2l_launch_embed(const float* x, long long total, int L, float* emb_out,
                             hipStream_t stream);

@@ -96,8 +96,9 @@ __global__ void r2l_sample_embed_kernel(R2LParams p, float* __restrict__ pts_out
         float pw = 1.0f;
 #pragma unroll
         for (int l = 0; l < R2L_L; ++l) {
-            e[l] = trig_pow2(r, pw, false);
-            e[R2L_L + l] = trig_pow2(r, pw, true);
+            const bool fin = embed_arg_finite(x, pw);     // x 2^l overflows: sin(inf) = NaN, as the reference
+            e[l] = fin ? trig_pow2(r, pw, false) : __builtin_nanf("");
+            e[R2L_L + l] = fin ? trig_pow2(r, pw, true) : __builtin_nanf("");
             pw *= 2.0f;
         }
         e[2 * R2L_L] = x;
@@ -113,11 +114,41 @@ __global__ void r2l_embed_kernel(const float* __restrict__ x_in, long long total
     Rev r = to_rev(x);
     float pw = 1.0f;
     for (int l = 0; l < L; ++l) {
-        e[l] = trig_pow2(r, pw, false);
-        e[L + l] = trig_pow2(r, pw, true);
+        const bool fin = embed_arg_finite(x, pw);
+        e[l] = fin ? trig_pow2(r, pw, false) : __builtin_nanf("");
+        e[L + l] = fin ? trig_pow2(r, pw, true) : __builtin_nanf("");
         pw *= 2.0f;
     }
     e[2 * L] = x;
+}
+
+// ------------------------------------------------------------------------------------
+// non-finite rays.  The reference renders a ray as NaN when its embedding holds one: a NaN or infinite point, or a
+// point whose x 2^9 overflows -- every head feature is then NaN, relu keeps it (torch), and all three channels are NaN.  The fused
+// renderers' ReLU (fmaxf here, v_max in the generated streams) drops the NaN and goes on with h0 = 0, so the rule is applied where it
+// depends on nothing but the ray: one thread per ray behind the last launch of the call restates make_ray + sample_pt and overwrites
+// the rgb of such a ray.  Reads 24 B per given ray; writes only what it marks.
+// ------------------------------------------------------------------------------------
+__global__ void r2l_mark_nonfinite_kernel(R2LParams p) {
+    const unsigned uray = blockIdx.x * blockDim.x + threadIdx.x;      // n_rays < 2^31: no wrap
+    if (uray >= (unsigned)p.n_rays) return;
+    const int ray = (int)uray;
+    const Ray6 r = make_ray(p, ray);
+    bool fin = true;
+    for (int s = 0; s < R2L_NSAMPLE; ++s) {
+        const float z = p.z[s];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) fin = fin && embed_arg_finite(sample_pt(r.o(k), r.d(k), z), 512.0f);
+    }
+    if (!fin) {
+        float* out = p.rgb + (size_t)ray * 3;
+        out[0] = out[1] = out[2] = __builtin_nanf("");
+    }
+}
+
+hipError_t r2l_launch_mark_nonfinite(const R2LParams& p, hipStream_t stream) {
+    hipLaunchKernelGGL(r2l_mark_nonfinite_kernel, dim3((unsigned)(((long long)p.n_rays + 255) / 256)), dim3(256), 0, stream, p);
+    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------

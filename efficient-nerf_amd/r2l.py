@@ -16,6 +16,7 @@ handles runs the stand-alone HIP kernels instead, which is what the parity tests
 """
 import ctypes as C
 import math
+import sys
 
 import torch
 
@@ -33,6 +34,23 @@ def _dev(device=None):
     if not torch.cuda.is_available():
         raise R2LError('no HIP device visible to torch: the R2L path has no CPU fallback')
     return torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+
+
+def watch_diff(got, ref, owner=None):
+    """What every watch compares two renders of the same rays with.  A ray with a NaN in its embedding renders as NaN in every mode
+    (DESIGN.md §4), so a NaN on both sides is agreement, not a miss: the largest |got - ref| over the elements that are numbers on both
+    sides.  Where the NaN masks differ the result is NaN, which fails every `d <= limit`.  A sample that is NaN on both sides throughout
+    compares nothing: 0.0, counted in `owner.watch_all_nan` and said on stderr."""
+    both = torch.isnan(got) & torch.isnan(ref)
+    if got.numel() == 0:
+        return 0.0
+    d = float(torch.where(both, torch.zeros_like(got), (got - ref).abs()).max())     # a NaN on one side only stays one
+    if d == 0.0 and bool(both.all()):
+        if owner is not None:
+            owner.watch_all_nan = getattr(owner, 'watch_all_nan', 0) + 1
+        print(f'[precision] watch: all {got.numel()} sampled values are NaN in both renders (non-finite rays): nothing compared, '
+              f'difference 0', file=sys.stderr)
+    return d
 
 
 def _c2w_host(c2w):
@@ -363,7 +381,7 @@ class R2LEngine:
                 self.set_precision(mode)
             got = self._probe_render(c2w, rays).clone()
             self.set_precision(PREC_FP16X3_ASM)
-            self.auto_verify = float((got - self._probe_render(c2w, rays)).abs().max())
+            self.auto_verify = watch_diff(got, self._probe_render(c2w, rays), self)
             if self.auto_verify <= self.AUTO_VERIFY_MAX_DIFF:
                 self.set_precision(mode)
                 self.range_status(reset=True)
@@ -468,7 +486,7 @@ class R2LEngine:
                     return 0.0
                 if sp not in tried:
                     self.set_split_block(sp)
-                    tried[sp] = float((rend() - ref).abs().max())
+                    tried[sp] = watch_diff(rend(), ref, self)
                 return tried[sp]
 
             def ok(sp):
@@ -522,7 +540,7 @@ class R2LEngine:
             ref = self.render_rays(ro, rd)
         finally:
             self.set_split_block(sp)
-        d = float((got - ref).abs().max())
+        d = watch_diff(got, ref, self)
         return d <= self.SPLIT_WATCH_MAX_DIFF, d
 
     def step_down_split(self):
@@ -575,7 +593,7 @@ class R2LEngine:
         ro, rd = self._strided_rays(rays_o, rays_d, n_rays or self.WHOLE_WATCH_RAYS)
         got = self.render_rays(ro, rd)
         ref = self._watch_engine().render_rays(ro, rd)
-        d = float((got - ref).abs().max())
+        d = watch_diff(got, ref, self)
         self.whole_watch_checks = getattr(self, 'whole_watch_checks', 0) + 1
         return d <= self.WHOLE_WATCH_MAX_DIFF, d
 

@@ -17,7 +17,12 @@ import torch
 
 from . import _lib
 from ._lib import R2LError, PREC_FP16X1, PREC_FP16X3, check, current_stream, dptr, lib
-from .r2l import _c2w_host, _dev
+from .r2l import _c2w_host, _dev, watch_diff
+
+
+def _nanmax(a, b):
+    """max of two differences that keeps a NaN (a NaN-mask mismatch, watch_diff) whichever side it is on; Python's max drops one"""
+    return a if a != a else b if b != b else max(a, b)
 
 
 def _f32(t, device):
@@ -429,9 +434,9 @@ class NeRFEngine:
             per_set, ok = [], True
             for (ro, rd), ref in zip(probes, refs):
                 got = self.render_rays(ro, rd)
-                d = {k: float((got[k] - ref[k]).abs().max()) for k in ref}
+                d = {k: watch_diff(got[k], ref[k], self) for k in ref}
                 per_set.append(d)
-                ok = ok and all(d[k] <= lim[k] for k in d)               # NaN fails
+                ok = ok and all(d[k] <= lim[k] for k in d)               # NaN (the two NaN masks differ) fails
             diff = max(max(d['rgb_map'], d['acc_map']) for d in per_set)
             self.auto_diffs[name] = diff
             self.auto_detail[name] = per_set
@@ -515,10 +520,10 @@ class NeRFEngine:
         """{output: largest difference} over WATCH_KEYS; acc / depth without the rays of `tie` (their number as 'far_plane_ties')"""
         d = {}
         for k in self.WATCH_KEYS:
-            e = (got[k] - ref[k]).abs()
+            g, r = got[k], ref[k]
             if tie is not None and k != 'rgb_map' and bool(tie.any()):
-                e = e[~tie]
-            d[k] = float(e.max()) if e.numel() else 0.0
+                g, r = g[~tie], r[~tie]
+            d[k] = watch_diff(g, r, self)
         if tie is not None:
             d['far_plane_ties'] = int(tie.sum())
         return d
@@ -531,7 +536,7 @@ class NeRFEngine:
         lim = self._limits(self.AUTO_MAX_DIFF_X3ASM)
         lim['rgb0'] = lim['acc0'] = self.AUTO_MAX_DIFF_X3ASM
         got = self.render_rays(ro, rd, extras=True)
-        d = {k: float((got[k] - ref[k]).abs().max()) for k in ('rgb0', 'acc0')}
+        d = {k: watch_diff(got[k], ref[k], self) for k in ('rgb0', 'acc0')}
         vd = None
         if self.ndc:
             vd = rd / torch.norm(rd, dim=-1, keepdim=True)
@@ -540,7 +545,7 @@ class NeRFEngine:
         rgb, _, acc, _, depth = raw2outputs(raw, ref['z_vals'], rd, white_bkgd=self.white_bkgd)
         tie = self._far_ties(raw, ref['raw']) if 'raw' in ref else None
         d.update(self._map_diffs({'rgb_map': rgb, 'acc_map': acc, 'depth_map': depth}, ref, tie))
-        return d, all(d[k] <= lim[k] for k in lim)       # NaN fails
+        return d, all(d[k] <= lim[k] for k in lim)       # NaN (the two NaN masks differ) fails
 
     @property
     def precision_name(self):
@@ -589,7 +594,7 @@ class NeRFEngine:
                 self.set_precision(cur)
             d = self._map_diffs(mine, ref, self._far_ties(mine['raw'], ref['raw']))
             # (what was rendered for the whole set is this mode's render of these rays: a ray's result does not depend on its batch)
-            d['rgb_map'] = max(d['rgb_map'], float((got['rgb_map'].reshape(-1, 3)[idx] - ref['rgb_map']).abs().max()))
+            d['rgb_map'] = _nanmax(d['rgb_map'], watch_diff(got['rgb_map'].reshape(-1, 3)[idx], ref['rgb_map'], self))
             self.watch_checks = getattr(self, 'watch_checks', 0) + 1
             return all(d[k] <= lim[k] for k in self.WATCH_KEYS), d
         self.set_precision(PREC_FP16X3)
@@ -597,7 +602,7 @@ class NeRFEngine:
             ref = self.render_rays(ro[idx].contiguous(), rd[idx].contiguous())
         finally:
             self.set_precision(cur)
-        d = {k: float((got[k].reshape((-1,) + tuple(ref[k].shape[1:]))[idx] - ref[k]).abs().max()) for k in self.WATCH_KEYS}
+        d = {k: watch_diff(got[k].reshape((-1,) + tuple(ref[k].shape[1:]))[idx], ref[k], self) for k in self.WATCH_KEYS}
         self.watch_checks = getattr(self, 'watch_checks', 0) + 1
         return all(d[k] <= lim[k] for k in d), d
 

@@ -113,3 +113,92 @@ def scan_reference(n, S, kind, white, with_noise):
 
 def scan_combos():
     return [(kind, white, with_noise) for kind in KINDS for white in (False, True) for with_noise in (False, True)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Non-finite RAYS of the fused renderers (tests/test_render_nonfinite_gpu.py, tests/test_teacher_nonfinite_gpu.py): the six poisons of
+# DESIGN.md §4's table, a set of rays with some of them poisoned beside the same set with each poisoned ray replaced by a copy of the
+# clean ray next to it (a duplicate adds no new maximum to any statistic of the launch), and output buffers that show what was written.
+# ---------------------------------------------------------------------------------------------------------------------------------
+RAY_POISONS = ('o.x=nan', 'o.y=+inf', 'd.z=nan', 'd.x=-inf', 'd=0', 'o.x=3e38')
+STUDENT_NAN = (True, True, True, True, False, True)       # the student's rgb of such a ray: all three channels NaN, or finite
+#: the teacher's outputs that are NaN for poison 4 (the view directions are 0 / 0, the density branch stays finite: acc = depth = 0, disp = 0 / 0);
+#: for every other poison all of them are
+TEACHER_KEYS = ('rgb_map', 'disp_map', 'acc_map', 'depth_map', 'rgb0', 'acc0', 'z_std')
+TEACHER_NAN_D0 = {'rgb_map': True, 'disp_map': True, 'acc_map': False, 'depth_map': False, 'rgb0': True, 'acc0': False, 'z_std': False}
+SENTINEL = 0x7FA5A5A5        # a NaN no kernel produces (theirs is 0x7FC00000): compared as bits
+GUARD = 64                   # words behind every output that must keep the sentinel
+
+
+def poison_ray(ro, rd, r, kind):
+    """poison `kind` (index into RAY_POISONS) on ray r of the CPU tensors ro, rd [n, 3], in place"""
+    if kind == 0:
+        ro[r, 0] = NAN
+    elif kind == 1:
+        ro[r, 1] = INF
+    elif kind == 2:
+        rd[r, 2] = NAN
+    elif kind == 3:
+        rd[r, 0] = -INF
+    elif kind == 4:
+        rd[r] = 0.
+    elif kind == 5:
+        ro[r, 0] = 3e38
+    else:
+        raise ValueError(kind)
+
+
+def frame_rays(H, W, n=None, theta=30., phi=-30., radius=4.):
+    """the first n rays (default all) of the frame of pose_spherical(theta, phi, radius): CPU float32 [n, 3] x 2, focal"""
+    focal = O.focal_from_angle(W)
+    ro, rd = O.get_rays(H, W, focal, O.pose_spherical(theta, phi, radius)[:3, :4])
+    ro, rd = ro.reshape(-1, 3).float()[:n].contiguous().clone(), rd.reshape(-1, 3).float()[:n].contiguous().clone()
+    return ro, rd, focal
+
+
+def poisoned_pair(ro, rd, positions, shift=0):
+    """(bad_o, bad_d, dup_o, dup_d, kinds): position i of `positions` gets poison (i + shift) % 6 in `bad`; in `dup` it holds a copy of the
+    nearest ray that is not poisoned (the one behind it, in front of it at the end of the set).  kinds: {ray: poison}."""
+    n = ro.shape[0]
+    bad_o, bad_d, dup_o, dup_d = ro.clone(), rd.clone(), ro.clone(), rd.clone()
+    kinds = {int(r): (i + shift) % len(RAY_POISONS) for i, r in enumerate(positions)}
+    for r, k in kinds.items():
+        poison_ray(bad_o, bad_d, r, k)
+        src = next(c for c in list(range(r + 1, n)) + list(range(r - 1, -1, -1)) if c not in kinds)
+        dup_o[r], dup_d[r] = ro[src], rd[src]
+    return bad_o, bad_d, dup_o, dup_d, kinds
+
+
+def clean_mask(n, kinds):
+    m = torch.ones(n, dtype=torch.bool)
+    m[list(kinds)] = False
+    return m
+
+
+def sentinel_like(shape, device):
+    """(out, whole): `out` of `shape`, a view of the front of the flat buffer `whole`, which is GUARD words longer; every word the sentinel"""
+    numel = 1
+    for s in shape:
+        numel *= int(s)
+    whole = torch.full((numel + GUARD,), SENTINEL, dtype=torch.int32, device=device).view(torch.float32)
+    return whole[:numel].view(*shape), whole
+
+
+def written_exactly(out, whole):
+    """every word of `out` was written and none behind it"""
+    bits = whole.view(torch.int32)
+    n = out.numel()
+    return bool((bits[:n] != SENTINEL).all()) and bool((bits[n:] == SENTINEL).all())
+
+
+def no_new_inf(got, want):
+    """no +-Inf in `got` where the oracle's `want` has none"""
+    return not bool((torch.isinf(got) & ~torch.isinf(want)).any())
+
+
+def int32_equal(a, b, rows=None):
+    """bit for bit, NaN payloads included; `rows`: a boolean mask over the first dimension"""
+    a, b = a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)
+    if rows is not None:
+        a, b = a[rows], b[rows]
+    return a.shape == b.shape and torch.equal(a, b)
