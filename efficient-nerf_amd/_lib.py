@@ -143,6 +143,8 @@ SIGNATURES = {
                             _vp, _vp, _vp, C.c_longlong, _vp]),
     # teacher training (csrc/nerf_train.hip)
     'nerf_train_raw2outputs_backward': (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
+    'nerf_train_batch_rays': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_longlong, C.c_int, C.c_float, _vp, _vp, _vp,
+                                        _vp, _vp]),
 }
 
 _lib = None

@@ -27,6 +27,7 @@
 #include "../../include/r2l_hip.h"
 #include "nerf_kernels.h"
 #include "r2l_device.h"
+#include "r2l_ray_math.h"
 
 // ====================================================================================
 // MLP
@@ -609,31 +610,26 @@ __global__ void nerf_get_rays_kernel(float c00, float c01, float c02, float c03,
 // reference's operation order, one rounding per operation.
 //   c0 = fl32(-1/(W/(2 focal))), c1 = fl32(-1/(H/(2 focal))), two_near = fl32(2 near), mtwo_near = fl32(-2 near)
 // ====================================================================================
-__global__ void nerf_ndc_rays_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d, int n, float c0,
-                                     float c1, float near_, float two_near, float mtwo_near, float* __restrict__ out_o,
-                                     float* __restrict__ out_d, float* __restrict__ viewdirs) {
+__global__ void nerf_ndc_rays_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d, int n, RayNdc k,
+                                     float* __restrict__ out_o, float* __restrict__ out_d, float* __restrict__ viewdirs) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const float ox = rays_o[(size_t)i * 3], oy = rays_o[(size_t)i * 3 + 1], oz = rays_o[(size_t)i * 3 + 2];
-    const float dx = rays_d[(size_t)i * 3], dy = rays_d[(size_t)i * 3 + 1], dz = rays_d[(size_t)i * 3 + 2];
+    const float o[3] = {rays_o[(size_t)i * 3], rays_o[(size_t)i * 3 + 1], rays_o[(size_t)i * 3 + 2]};
+    const float d[3] = {rays_d[(size_t)i * 3], rays_d[(size_t)i * 3 + 1], rays_d[(size_t)i * 3 + 2]};
     if (viewdirs) {  // rays_d / ||rays_d|| of the WORLD rays (same arithmetic as nerf_mlp_kernel)
-        const float nrm = sqrtf(__fadd_rn(__fadd_rn(dx * dx, dy * dy), dz * dz));
-        viewdirs[(size_t)i * 3] = __fdiv_rn(dx, nrm);
-        viewdirs[(size_t)i * 3 + 1] = __fdiv_rn(dy, nrm);
-        viewdirs[(size_t)i * 3 + 2] = __fdiv_rn(dz, nrm);
+        float v[3];
+        ray_viewdir(d, v);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) viewdirs[(size_t)i * 3 + c] = v[c];
     }
     if (!out_o) return;
-    const float t = __fdiv_rn(-__fadd_rn(near_, oz), dz);       // -(near + o_z) / d_z
-    const float px = __fadd_rn(ox, __fmul_rn(t, dx));            // origin moved to the near plane
-    const float py = __fadd_rn(oy, __fmul_rn(t, dy));
-    const float pz = __fadd_rn(oz, __fmul_rn(t, dz));
-    const float rx = __fdiv_rn(px, pz), ry = __fdiv_rn(py, pz);  // used by the d0 / d1 terms
-    out_o[(size_t)i * 3] = __fdiv_rn(__fmul_rn(c0, px), pz);     // (c0 * o_x) / o_z
-    out_o[(size_t)i * 3 + 1] = __fdiv_rn(__fmul_rn(c1, py), pz);
-    out_o[(size_t)i * 3 + 2] = __fadd_rn(1.0f, __fdiv_rn(two_near, pz));
-    out_d[(size_t)i * 3] = __fmul_rn(c0, __fadd_rn(__fdiv_rn(dx, dz), -rx));
-    out_d[(size_t)i * 3 + 1] = __fmul_rn(c1, __fadd_rn(__fdiv_rn(dy, dz), -ry));
-    out_d[(size_t)i * 3 + 2] = __fdiv_rn(mtwo_near, pz);
+    float po[3], pd[3];
+    ray_ndc_project(k, o, d, po, pd);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        out_o[(size_t)i * 3 + c] = po[c];
+        out_d[(size_t)i * 3 + c] = pd[c];
+    }
 }
 
 // ====================================================================================
@@ -1135,9 +1131,8 @@ hipError_t nerf_launch_mlp(const NerfMlpParams& p, int mode, int grid, hipStream
 
 hipError_t nerf_launch_ndc_rays(const float* rays_o, const float* rays_d, int n, int H, int W, double focal, float near_,
                                 float* out_o, float* out_d, float* viewdirs, hipStream_t stream) {
-    const float c0 = (float)(-1. / (W / (2. * focal))), c1 = (float)(-1. / (H / (2. * focal)));
-    hipLaunchKernelGGL(nerf_ndc_rays_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, rays_o, rays_d, n, c0, c1, near_,
-                       (float)(2. * near_), (float)(-2. * near_), out_o, out_d, viewdirs);
+    hipLaunchKernelGGL(nerf_ndc_rays_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, rays_o, rays_d, n,
+                       ray_ndc_constants(H, W, focal, near_), out_o, out_d, viewdirs);
     return hipGetLastError();
 }
 

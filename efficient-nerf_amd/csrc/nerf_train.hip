@@ -1,5 +1,6 @@
 // Training of the NeRF teacher (main.py:624-756, 1353-1406) in exact fp32: the one stage of a teacher step the student's
-// training kernels (r2l_train.hip) do not cover, the backward pass of the volume-rendering scan raw2outputs (main.py:556-621).
+// training kernels (r2l_train.hip) do not cover, the backward pass of the volume-rendering scan raw2outputs (main.py:556-621),
+// and, further down, the rays of a step of the use_batching loop straight from the images (nerf_train_batch_rays_kernel).
 // The host mirror composes the step (efficient-nerf_amd/train_teacher.py).
 //
 // Forward (nerf_raw2outputs_kernel): c = sigmoid(raw_rgb), s = relu(raw_sigma + noise), alpha = 1 - exp(-s dist),
@@ -24,6 +25,7 @@
 
 #include "../../include/r2l_hip.h"
 #include "r2l_host_util.h"
+#include "r2l_ray_math.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -152,6 +154,61 @@ __global__ __launch_bounds__(256) void nerf_raw2outputs_backward_kernel(const fl
     }
 }
 
+// ---- a step's rays straight from the images (the reference's use_batching loop, main.py:1137-1162, 1199-1210) -----------------
+// The reference keeps rays_rgb [n_train H W, 3, 3] (get_rays_np of every training pose beside the images) and slices N_rand rows of
+// it per step.  That bank is a function of the image bytes, the poses and a permutation, so those stay on the device and a step's
+// rows are computed: thread t of a block owns output ray k = 256 block + t, src = order[k] names image src / (H W) and pixel
+// (row, column) of its grid.  Colour and world ray are r2l_rays_from_images_kernel's (three channels, full resolution), the view
+// direction and the NDC projection nerf_ndc_rays_kernel's: the device code is shared (r2l_ray_math.h), not restated.
+// Reads: 8 bytes of order (coalesced), then a random 3-byte pixel and a 48-byte pose (a handful of poses: cache hits).  Stores: the
+// block's 256 rows of each output are 768 consecutive floats, staged in LDS and written as consecutive dwords by consecutive
+// lanes, 256 bytes per wave instruction, whatever the alignment of the four arrays.  No atomics: a pure function of the inputs.
+// An index outside [0, n_img H W) reads nothing and gives NaN in all four rows.
+__global__ void __launch_bounds__(256) nerf_train_batch_rays_kernel(const unsigned char* __restrict__ images, long long n_img, int H, int W,
+                                                                     const float* __restrict__ poses, float half_w, float half_h, float focal,
+                                                                     const long long* __restrict__ order, long long rows, int ndc, RayNdc kn,
+                                                                     float* __restrict__ rays_o, float* __restrict__ rays_d,
+                                                                     float* __restrict__ viewdirs, float* __restrict__ target) {
+    __shared__ float stage[4][768];
+    const int t = threadIdx.x;
+    const long long base = (long long)blockIdx.x * 256;
+    const long long k = base + t;
+    if (k < rows) {
+        const float nan = __builtin_nanf("");
+        float o[3] = {nan, nan, nan}, d[3] = {nan, nan, nan}, v[3] = {nan, nan, nan}, c[3] = {nan, nan, nan};
+        const long long per_img = (long long)H * W;
+        const long long src = order[k];
+        if (src >= 0 && src < n_img * per_img) {
+            const long long img = src / per_img;
+            const int pix = (int)(src - img * per_img);
+            const int j = pix / W, i = pix - j * W;
+            ray_load_pixel<3>(images + ((size_t)img * per_img + pix) * 3, c);
+            ray_from_pixel(poses + img * 12, i, j, half_w, half_h, focal, o, d);
+            ray_viewdir(d, v);                        // of the WORLD direction, before the projection (main.py:148-162)
+            if (ndc) ray_ndc_project(kn, o, d, o, d);
+        }
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            stage[0][3 * t + r] = o[r];
+            stage[1][3 * t + r] = d[r];
+            stage[2][3 * t + r] = v[r];
+            stage[3][3 * t + r] = c[r];
+        }
+    }
+    __syncthreads();
+    const long long left = rows - base;
+    const int count = 3 * (int)(left < 256 ? left : 256);     // floats of this block per output
+    float* const outs[4] = {rays_o, rays_d, viewdirs, target};
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        if (!outs[a]) continue;                               // viewdirs may be NULL
+        float* __restrict__ dst = outs[a] + base * 3;
+#pragma unroll
+        for (int e = t; e < 768; e += 256)
+            if (e < count) dst[e] = stage[a][e];
+    }
+}
+
 extern "C" {
 
 int nerf_train_raw2outputs_backward(const float* raw_dev, const float* z_dev, const float* rays_d_dev, const float* noise_dev, int n,
@@ -169,6 +226,30 @@ int nerf_train_raw2outputs_backward(const float* raw_dev, const float* z_dev, co
                        rays_d_dev, noise_dev, n, S, white_bkgd ? 1 : 0, g_rgb_map_dev, g_raw_dev);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "nerf_train_raw2outputs_backward launch: %s", hipGetErrorString(e));
+    return R2L_OK;
+}
+
+int nerf_train_batch_rays(const unsigned char* images_dev, int n_img, int H, int W, const float* poses_dev, double focal,
+                          const long long* order_dev, long long rows, int ndc, float near_, float* rays_o_dev, float* rays_d_dev,
+                          float* viewdirs_dev, float* target_dev, void* stream) {
+    if (!images_dev || !poses_dev || n_img <= 0 || H <= 0 || W <= 0 || rows < 0 ||
+        (rows != 0 && (!order_dev || !rays_o_dev || !rays_d_dev || !target_dev)))
+        return r2l_set_error(R2L_EINVAL, "bad argument to nerf_train_batch_rays (n_img=%d H=%d W=%d rows=%lld)", n_img, H, W, rows);
+    if (!(focal > 0.0)) return r2l_set_error(R2L_EINVAL, "nerf_train_batch_rays: focal = %g", focal);
+    if (ndc && !(near_ == near_)) return r2l_set_error(R2L_EINVAL, "nerf_train_batch_rays: near = %g", (double)near_);
+    if (((uintptr_t)poses_dev & 3) || ((uintptr_t)rays_o_dev & 3) || ((uintptr_t)rays_d_dev & 3) || ((uintptr_t)viewdirs_dev & 3) ||
+        ((uintptr_t)target_dev & 3) || ((uintptr_t)order_dev & 7))
+        return r2l_set_error(R2L_EINVAL, "nerf_train_batch_rays: poses and the four outputs must be 4-byte aligned, order 8-byte aligned");
+    if ((rows + 255) / 256 > 0x7fffffffll) return r2l_set_error(R2L_EINVAL, "nerf_train_batch_rays: rows = %lld", rows);
+    int rc = r2l_require_gfx950(nullptr);
+    if (rc) return rc;
+    if (rows == 0) return R2L_OK;
+    const float half_w = (float)(W * .5), half_h = (float)(H * .5);
+    hipLaunchKernelGGL(nerf_train_batch_rays_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, (hipStream_t)stream, images_dev,
+                       (long long)n_img, H, W, poses_dev, half_w, half_h, (float)focal, order_dev, rows, ndc ? 1 : 0,
+                       ray_ndc_constants(H, W, focal, near_), rays_o_dev, rays_d_dev, viewdirs_dev, target_dev);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "nerf_train_batch_rays launch: %s", hipGetErrorString(e));
     return R2L_OK;
 }
 

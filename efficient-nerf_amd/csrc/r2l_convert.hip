@@ -16,21 +16,9 @@
 
 #include "../../include/r2l_hip.h"
 #include "r2l_host_util.h"
+#include "r2l_ray_math.h"
 
 namespace {
-
-// one pixel's channels as bytes / 255
-template <int C>
-__device__ __forceinline__ void load_pixel(const unsigned char* __restrict__ p, float (&v)[C]) {
-    if constexpr (C == 4) {
-        const uint32_t w = *reinterpret_cast<const uint32_t*>(p);       // 4-byte aligned: the base is, and a pixel is 4 bytes
-#pragma unroll
-        for (int c = 0; c < 4; ++c) v[c] = __fdiv_rn((float)((w >> (8 * c)) & 0xffu), 255.0f);
-    } else {
-#pragma unroll
-        for (int c = 0; c < C; ++c) v[c] = __fdiv_rn((float)p[c], 255.0f);
-    }
-}
 
 template <int C>
 __global__ void __launch_bounds__(256) r2l_rays_from_images_kernel(const unsigned char* __restrict__ images, long long n_img, int H0, int W0,
@@ -56,14 +44,14 @@ __global__ void __launch_bounds__(256) r2l_rays_from_images_kernel(const unsigne
     if (half_res) {
         float a[C], b[C], c_[C], d[C];
         const size_t at = ((size_t)(2 * j) * W0 + 2 * i) * C;
-        load_pixel<C>(im + at, a);
-        load_pixel<C>(im + at + C, b);
-        load_pixel<C>(im + at + (size_t)W0 * C, c_);
-        load_pixel<C>(im + at + (size_t)W0 * C + C, d);
+        ray_load_pixel<C>(im + at, a);
+        ray_load_pixel<C>(im + at + C, b);
+        ray_load_pixel<C>(im + at + (size_t)W0 * C, c_);
+        ray_load_pixel<C>(im + at + (size_t)W0 * C + C, d);
 #pragma unroll
         for (int c = 0; c < C; ++c) v[c] = __fmul_rn(__fadd_rn(__fadd_rn(a[c], b[c]), __fadd_rn(c_[c], d[c])), 0.25f);
     } else {
-        load_pixel<C>(im + ((size_t)j * W0 + i) * C, v);
+        ray_load_pixel<C>(im + ((size_t)j * W0 + i) * C, v);
     }
     if constexpr (C == 4) {
         const float one_minus_a = __fsub_rn(1.0f, v[3]);
@@ -72,13 +60,12 @@ __global__ void __launch_bounds__(256) r2l_rays_from_images_kernel(const unsigne
     }
     // ray
     const float* __restrict__ p = poses + img * 12;
-    const float dx = __fdiv_rn(__fsub_rn((float)i, half_w), focal);
-    const float dy = -__fdiv_rn(__fsub_rn((float)j, half_h), focal);
+    float ro[3], rd[3];
+    ray_from_pixel(p, i, j, half_w, half_h, focal, ro, rd);
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-        const float s = __fadd_rn(__fmul_rn(dx, p[4 * r + 0]), __fmul_rn(dy, p[4 * r + 1]));
-        o[r] = p[4 * r + 3];
-        o[3 + r] = __fadd_rn(s, __fmul_rn(-1.0f, p[4 * r + 2]));
+        o[r] = ro[r];
+        o[3 + r] = rd[r];
         o[6 + r] = v[r];
     }
 }

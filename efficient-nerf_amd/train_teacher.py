@@ -1,7 +1,8 @@
-"""Training of the NeRF teacher (main.py:1136-1513 with --model_name nerf, --data_mode images, no_batching; the step is
-render_rays, main.py:624-756, under autograd plus torch.optim.Adam): both networks' forward and backward passes, both
-volume-rendering scans and their backward pass, the two rgb losses and Adam as launches of the library's fp32 kernels
-(csrc/r2l_generic.hip, r2l_train.hip, nerf_kernels.hip, nerf_train.hip; include/r2l_hip.h).
+"""Training of the NeRF teacher (main.py:1136-1513 with --model_name nerf, --data_mode images: no_batching on Blender scenes,
+use_batching on LLFF scenes; the step is render_rays, main.py:624-756, under autograd plus torch.optim.Adam): both networks'
+forward and backward passes, both volume-rendering scans and their backward pass, the two rgb losses and Adam as launches of the
+library's fp32 kernels (csrc/r2l_generic.hip, r2l_train.hip, nerf_kernels.hip, nerf_train.hip; include/r2l_hip.h).  On LLFF a
+step's rays come from the image bytes in one launch (RayBatches, nerf_train_batch_rays).
 
 NeRFTrainer holds the coarse network's parameters, then the fine one's, in one flat device buffer (flat_trainer.FlatAdam), and the
 saved output of every layer of both passes for the backward pass.  torch supplies the buffers, the stream and the random draws
@@ -321,7 +322,7 @@ class NeRFTrainer(FlatAdam):
             raise R2LError(f'{what} is {tuple(t.shape)}, expected {tuple(shape)}')
         return t
 
-    def forward_backward(self, rays_o, rays_d, target, perturb=1., raw_noise_std=0., t_rand=None, u=None, noise=None):
+    def forward_backward(self, rays_o, rays_d, target, perturb=1., raw_noise_std=0., t_rand=None, u=None, noise=None, viewdirs=None):
         """loss = img2mse(rgb, target) + img2mse(rgb0, target) (a one-element device tensor; the coarse term alone with
         N_importance = 0); the gradients are left in the flat buffer (grads()).
 
@@ -329,12 +330,16 @@ class NeRFTrainer(FlatAdam):
         N_importance]) (what is added to the density in front of its relu: randn * raw_noise_std) replace the draws of main.py:691,
         helpers:298-307 and main.py:592-598; by default they are torch draws on the device.  self.last keeps the step's detached
         quantities: per pass the embedded inputs (`emb0`, `emb1`: [n * S, input_ch]; `dirs0`, `dirs1`: the embedded view
-        directions), the depths (`z0`, `z1`), the noise, `raw0` / `raw1`, and `rgb0` / `rgb`."""
+        directions), the depths (`z0`, `z1`), the noise, `raw0` / `raw1`, and `rgb0` / `rgb`.
+
+        viewdirs [n, 3]: unit view directions used in place of rays_d / ||rays_d|| -- those of the world-space rays when rays_o /
+        rays_d are their NDC projection (main.py:148-162); rays_o / rays_d are sampled and composited along as they are."""
         from .teacher import merge_sorted, sample_pdf
         self._need_state()
         n = rays_o.shape[0]
         dev = self.device
         ro, rd, tgt = self._on_device(n, rays_o=rays_o, rays_d=rays_d, target=target)
+        given_dirs = self._on_device(n, viewdirs=viewdirs)[0] if viewdirs is not None and self.use_viewdirs else None
         S0, Ni = self.N_samples, self.N_importance
         fine = Ni > 0
         noises = [None, None]
@@ -342,7 +347,9 @@ class NeRFTrainer(FlatAdam):
             given = noise if noise is not None else (None, None)
             noises = [self._draw(given[k], (n, net.S), f'noise[{k}]', raw_noise_std) for k, net in enumerate(self.nets)]
         with torch.cuda.device(dev):
-            viewdirs = rd / torch.norm(rd, dim=-1, keepdim=True) if self.use_viewdirs else None      # main.py:148-157
+            viewdirs = given_dirs
+            if viewdirs is None and self.use_viewdirs:
+                viewdirs = rd / torch.norm(rd, dim=-1, keepdim=True)                                  # main.py:148-157
             if perturb > 0.:
                 z0 = jitter_z_vals(self._z_dev, n, self._draw(t_rand, (n, S0), 't_rand'))             # main.py:684-699
             else:
@@ -375,17 +382,80 @@ class NeRFTrainer(FlatAdam):
             self.loss_rgb = top.loss
             return c.loss + f.loss if fine else c.loss                                                 # main.py:1362-1380
 
-    def step(self, rays_o, rays_d, target, lr, perturb=1., raw_noise_std=0., t_rand=None, u=None, noise=None):
+    def step(self, rays_o, rays_d, target, lr, perturb=1., raw_noise_std=0., t_rand=None, u=None, noise=None, viewdirs=None):
         """forward_backward + Adam.  Returns (loss [1], loss_rgb [1]): the sum the gradients are of, and img2mse of the final rgb
         alone (what the reference's psnr line reports, main.py:1377-1379)."""
-        loss = self.forward_backward(rays_o, rays_d, target, perturb, raw_noise_std, t_rand, u, noise)
+        loss = self.forward_backward(rays_o, rays_d, target, perturb, raw_noise_std, t_rand, u, noise, viewdirs)
         self.adam(lr)
         return loss, self.loss_rgb
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# the loop of main.py:1136-1513 for --model_name nerf, --data_mode images, no_batching, Blender
+# the loop of main.py:1136-1513 for --model_name nerf, --data_mode images: no_batching on Blender, use_batching on LLFF
 # ---------------------------------------------------------------------------------------------------------------------------
+class RayBatches:
+    """The reference's use_batching loop (main.py:1141-1162, 1199-1210) without its bank rays_rgb [n, 3, 3]: row r of the bank is a
+    function of the image bytes, the poses and r, so the bytes [n_img, H, W, 3], the poses [n_img, 3, 4] and the order of the rows (an
+    int64 permutation of n = n_img * H * W, image-major, then row, then column) are what is kept on the device, and a step's rows
+    are computed by one launch (nerf_train_batch_rays).
+
+    The order follows the reference draw for draw: np.random.permutation(n) of the global numpy stream first (np.random.shuffle of
+    an [n, 3, 3] array walks the same Fisher-Yates over its first axis: the same draws, the same order), then after every epoch
+    perm = perm[torch.randperm(n)] from torch's CPU default generator.  A batch is the window [i_batch, i_batch + N_rand) cut at n:
+    the last batch of an epoch is short.  A resumed run starts a new epoch from a fresh draw (nothing of this is in a checkpoint).
+
+    near: ndc_rays' near plane (1 in the reference, main.py:162) when ndc."""
+
+    def __init__(self, image_bytes, poses, focal, N_rand, ndc, near=1., device=None, log=print):
+        image_bytes = torch.as_tensor(image_bytes)
+        if image_bytes.dtype != torch.uint8 or image_bytes.dim() != 4 or image_bytes.shape[-1] != 3:
+            raise R2LError(f'image bytes are {image_bytes.dtype} {tuple(image_bytes.shape)}, expected uint8 [n_img, H, W, 3]')
+        poses = torch.as_tensor(poses, dtype=torch.float32)[:, :3, :4]
+        self.n_img, self.H, self.W = (int(v) for v in image_bytes.shape[:3])
+        if tuple(poses.shape) != (self.n_img, 3, 4):
+            raise R2LError(f'poses are {tuple(poses.shape)} for {self.n_img} images')
+        self.focal, self.N_rand, self.ndc, self.near, self.log = float(focal), int(N_rand), bool(ndc), float(near), log
+        if self.N_rand < 1:
+            raise R2LError(f'N_rand {N_rand}')
+        self.n = self.n_img * self.H * self.W
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self._upload(image_bytes.contiguous(), poses.contiguous())
+        self.perm = torch.from_numpy(np.random.permutation(self.n).astype(np.int64))      # main.py:1156
+        self._set_order()
+        self.i_batch = 0
+
+    # the three places that touch the device (a test replaces them to follow the index stream on the host)
+    def _upload(self, image_bytes, poses):
+        self._bytes, self._poses = image_bytes.to(self.device), poses.to(self.device)
+
+    def _set_order(self):
+        self._order = self.perm.to(self.device)
+
+    def _launch(self, begin, rows):
+        f32 = dict(dtype=torch.float32, device=self.device)
+        out = torch.empty((4, rows, 3), **f32)
+        order = self._order[begin:begin + rows]             # a view: the permutation offset to the step's window
+        with torch.cuda.device(self.device):
+            check(lib().nerf_train_batch_rays(self._bytes.data_ptr(), self.n_img, self.H, self.W, dptr(self._poses), self.focal,
+                                              order.data_ptr(), rows, int(self.ndc), self.near, dptr(out[0]), dptr(out[1]), dptr(out[2]),
+                                              dptr(out[3]), current_stream()))
+        return out[0], out[1], out[2], out[3]
+
+    def next(self):
+        """(rays_o, rays_d, viewdirs, target) of the next step, each [rows, 3] on the device; rows = N_rand, fewer in an epoch's
+        last batch"""
+        begin = self.i_batch
+        rows = min(self.N_rand, self.n - begin)
+        batch = self._launch(begin, rows)
+        self.i_batch += self.N_rand                           # main.py:1205-1210
+        if self.i_batch >= self.n:
+            self.log('Shuffle data after an epoch!')
+            self.perm = self.perm[torch.randperm(self.n)]
+            self._set_order()
+            self.i_batch = 0
+        return batch
+
+
 def crop_bounds(H, W, precrop_frac):
     """main.py:1270-1278: the centre crop's (row0, rows, col0, cols)"""
     dH = int(H // 2 * precrop_frac)
@@ -407,6 +477,8 @@ def select_coords(H, W, N_rand, crop=None):
 REFUSALS = {
     'use_batching': 'use_batching (no --no_batching / no_batching = True): teacher training is built for one image per step',
     'llff': '--dataset_type {}: teacher training is built for Blender scenes (--dataset_type blender)',
+    'llff_no_batching': '--dataset_type llff: teacher training is built for Blender scenes with no_batching; LLFF scenes train with '
+                        'use_batching (no --no_batching / no_batching line, as configs/fern.txt)',
     'rand_patch': '--select_pixel_mode rand_patch: teacher training selects pixels with rand_pixel',
     'i_video': '--i_video {} falls inside this run: the video render is not built for training; pass an --i_video above --N_iters',
     'datadir_kd': '--datadir_kd with --data_mode images: pseudo images are not built for teacher training',
@@ -419,9 +491,12 @@ def check_supported(args, start=0):
     """one clear line for each mode of the reference's loop that is not built"""
     if args.model_name != 'nerf':
         raise SystemExit(REFUSALS['model_name'].format(args.model_name))
-    if not args.no_batching:
+    if args.dataset_type == 'llff':
+        if args.no_batching:
+            raise SystemExit(REFUSALS['llff_no_batching'])
+    elif not args.no_batching:
         raise SystemExit(REFUSALS['use_batching'])
-    if args.dataset_type != 'blender':
+    elif args.dataset_type != 'blender':
         raise SystemExit(REFUSALS['llff'].format(args.dataset_type))
     if args.select_pixel_mode != 'rand_pixel':
         raise SystemExit(REFUSALS['rand_patch'])
@@ -434,22 +509,23 @@ def check_supported(args, start=0):
     refuse_negative_i_testset(args)
 
 
-def trainer_from_args(args, max_rays):
-    return NeRFTrainer(2., 6., N_samples=args.N_samples, N_importance=args.N_importance, multires=args.multires,       # main.py:930-931
+def trainer_from_args(args, max_rays, near=2., far=6.):
+    """near, far: 2, 6 on Blender (main.py:930-931); on LLFF what llff_split_and_bounds gives"""
+    return NeRFTrainer(near, far, N_samples=args.N_samples, N_importance=args.N_importance, multires=args.multires,
                        multires_views=args.multires_views, i_embed=args.i_embed, netdepth=args.netdepth, netwidth=args.netwidth,
                        netdepth_fine=args.netdepth_fine, netwidth_fine=args.netwidth_fine, use_viewdirs=args.use_viewdirs,
                        white_bkgd=args.white_bkgd, lindisp=args.lindisp, max_rays=max_rays)
 
 
-def eval_test_split(trainer, args, hwf, poses, gt):
+def eval_test_split(trainer, args, hwf, poses, gt, near=2., far=6., ndc=False):
     """render_path over the test split from the current weights (main.py:1442-1456) on generic.GenericNeRF: (test_psnr, test_psnr_v2)"""
     from .frontend import mse2psnr
     from .generic import GenericNeRF
     H, W, focal = hwf
-    eng = GenericNeRF(H, W, focal, 2., 6., N_samples=args.N_samples, N_importance=args.N_importance, multires=args.multires,
+    eng = GenericNeRF(H, W, focal, near, far, N_samples=args.N_samples, N_importance=args.N_importance, multires=args.multires,
                       multires_views=args.multires_views, i_embed=args.i_embed, netdepth=args.netdepth, netwidth=args.netwidth,
                       netdepth_fine=args.netdepth_fine, netwidth_fine=args.netwidth_fine, use_viewdirs=args.use_viewdirs,
-                      white_bkgd=args.white_bkgd, lindisp=args.lindisp, device=trainer.device)
+                      white_bkgd=args.white_bkgd, lindisp=args.lindisp, ndc=ndc, device=trainer.device)
     eng.load_state_dicts(*trainer.state_dicts())
     mses = []
     for pose, img in zip(poses, gt):
@@ -458,37 +534,29 @@ def eval_test_split(trainer, args, hwf, poses, gt):
     return mse2psnr(float(np.mean(mses))), float(np.mean([mse2psnr(m) for m in mses]))
 
 
-def train(args, log=print):
-    """main.py without --render_only for --model_name nerf: returns the path of the last checkpoint"""
+def llff_split_and_bounds(scene, llffhold, no_ndc):
+    """main.py:903-919: (i_train, i_val, i_test, near, far) of a loaded LLFF scene.  Every llffhold-th view is held out (llffhold <= 0:
+    the loader's own view nearest the average pose), validation is the test set; NDC rays are sampled on [0, 1], world-space rays
+    (--no_ndc) from 0.9 x the nearest bound to the farthest."""
+    n = len(scene.poses)
+    i_test = np.arange(n)[::llffhold] if llffhold > 0 else np.array([scene.i_test])
+    i_val = i_test
+    i_train = np.array([i for i in np.arange(int(n)) if (i not in i_test and i not in i_val)])
+    if no_ndc:
+        near, far = float(np.ndarray.min(scene.bds) * .9), float(np.ndarray.max(scene.bds) * 1.)
+    else:
+        near, far = 0., 1.
+    return i_train, i_val, i_test, near, far
+
+
+def _blender_data(args, start, log):
+    """no_batching on a Blender scene (main.py:1212-1292): one training image per step, N_rand of its pixels, the centre crop"""
     from . import blender
-    from .frontend import load_checkpoint
     from .teacher import get_rays
-    start, ckpt = 0, None
-    if args.pretrained_ckpt:
-        ckpt = load_checkpoint(args.pretrained_ckpt)
-        if args.resume:
-            start = int(ckpt['global_step'])
-    check_supported(args, start)
     images, poses, hwf, (i_train, i_val, i_test) = blender.load_blender_data(args.datadir, args.half_res, args.testskip)
     images = blender.composite(images, args.white_bkgd)
     H, W, focal = int(hwf[0]), int(hwf[1]), float(hwf[2])
-    trainer = trainer_from_args(args, args.N_rand)
-    dev = trainer.device
-    best_psnr, best_psnr_step = 0., 0
-    if ckpt is not None:
-        trainer.load_state_dicts(ckpt['network_fn_state_dict'], ckpt.get('network_fine_state_dict'))
-        log(f'Load pretrained ckpt successfully: "{args.pretrained_ckpt}".')
-        if args.resume:                                       # main.py:504-509
-            trainer.load_optimizer_state_dict(ckpt['optimizer_state_dict'])
-            best_psnr, best_psnr_step = float(ckpt.get('best_psnr', 0.)), int(ckpt.get('best_psnr_step', 0))
-            log('Resume optimizer successfully.')
-    else:
-        trainer.load_state_dicts(*trainer.init_state_dicts())
-    weights_dir = os.path.join(args.basedir, args.expname or 'train_teacher', 'weights')
-    os.makedirs(weights_dir, exist_ok=True)
-    log(f'Loaded blender {tuple(images.shape)} from "{args.datadir}": {len(i_train)} train / {len(i_val)} val / {len(i_test)} test images, '
-        f'{H} x {W}, focal {focal:.4f}; {args.N_rand} rays per step, {args.N_samples} + {args.N_importance} samples; {trainer.n_param} '
-        f'parameters, {trainer.activation_bytes() / 2 ** 30:.2f} GiB of saved activations')
+    dev = torch.device('cuda', torch.cuda.current_device())
     crop = crop_bounds(H, W, args.precrop_frac)
 
     def draw(i):
@@ -501,14 +569,73 @@ def train(args, log=print):
         rows, cols = torch.as_tensor(rows, device=dev), torch.as_tensor(cols, device=dev)
         return rays_o[rows, cols], rays_d[rows, cols], images[img_i].to(dev)[rows, cols]
 
+    loaded = (f'Loaded blender {tuple(images.shape)} from "{args.datadir}": {len(i_train)} train / {len(i_val)} val / {len(i_test)} test '
+              f'images, {H} x {W}, focal {focal:.4f}')
+    return dict(hwf=(H, W, focal), bounds=(2., 6.), ndc=False, max_rays=args.N_rand, draw=draw, step_args={}, loaded=loaded,    # main.py:930-931
+                test=(poses[i_test], images[i_test]))
+
+
+def _llff_data(args, log):
+    """use_batching on an LLFF scene (main.py:890-919, 1137-1162, 1199-1210): random rays over all training images, no centre crop;
+    NDC unless --no_ndc"""
+    from . import llff
+    try:
+        scene = llff.load_scene(args.datadir, args.factor, spherify=args.spherify, n_pose_video=llff.n_pose_video_from_flag(args.n_pose_video))
+    except llff.LLFFError as e:
+        raise SystemExit(str(e))
+    H, W, focal = scene.hwf                                   # main.py:898: of poses[0]
+    i_train, i_val, i_test, near, far = llff_split_and_bounds(scene, args.llffhold, args.no_ndc)
+    ndc = not args.no_ndc
+    batches = RayBatches(scene.bytes[i_train], scene.poses[i_train][:, :3, :4], focal, args.N_rand, ndc, log=log)
+    step_args = {}
+
+    def draw(i):
+        rays_o, rays_d, viewdirs, target = batches.next()
+        step_args['viewdirs'] = viewdirs                      # run_iterations hands step_args to trainer.step beside the batch
+        return rays_o, rays_d, target
+
+    loaded = (f'Loaded llff {tuple(scene.bytes.shape)} from "{args.datadir}": {len(i_train)} train / {len(i_val)} val / {len(i_test)} test '
+              f'images, {H} x {W}, focal {focal:.4f}; {batches.n} training rays, near {near:.4f} far {far:.4f}{", NDC" if ndc else ""}')
+    return dict(hwf=(H, W, focal), bounds=(near, far), ndc=ndc, max_rays=min(args.N_rand, batches.n), draw=draw, step_args=step_args,
+                loaded=loaded, test=(torch.from_numpy(scene.poses[i_test][:, :3, :4].copy()), torch.from_numpy(scene.images[i_test])))
+
+
+def train(args, log=print):
+    """main.py without --render_only for --model_name nerf: returns the path of the last checkpoint"""
+    from .frontend import load_checkpoint
+    start, ckpt = 0, None
+    if args.pretrained_ckpt:
+        ckpt = load_checkpoint(args.pretrained_ckpt)
+        if args.resume:
+            start = int(ckpt['global_step'])
+    check_supported(args, start)
+    data = _llff_data(args, log) if args.dataset_type == 'llff' else _blender_data(args, start, log)
+    near, far = data['bounds']
+    trainer = trainer_from_args(args, data['max_rays'], near, far)
+    best_psnr, best_psnr_step = 0., 0
+    if ckpt is not None:
+        trainer.load_state_dicts(ckpt['network_fn_state_dict'], ckpt.get('network_fine_state_dict'))
+        log(f'Load pretrained ckpt successfully: "{args.pretrained_ckpt}".')
+        if args.resume:                                       # main.py:504-509
+            trainer.load_optimizer_state_dict(ckpt['optimizer_state_dict'])
+            best_psnr, best_psnr_step = float(ckpt.get('best_psnr', 0.)), int(ckpt.get('best_psnr_step', 0))
+            log('Resume optimizer successfully.')
+    else:
+        trainer.load_state_dicts(*trainer.init_state_dicts())
+    weights_dir = os.path.join(args.basedir, args.expname or 'train_teacher', 'weights')
+    os.makedirs(weights_dir, exist_ok=True)
+    log(f'{data["loaded"]}; {args.N_rand} rays per step, {args.N_samples} + {args.N_importance} samples; {trainer.n_param} '
+        f'parameters, {trainer.activation_bytes() / 2 ** 30:.2f} GiB of saved activations')
+
     def test_pass(i):                         # no further [TEST] fields, no line after it
-        test_psnr, test_psnr_v2 = eval_test_split(trainer, args, (H, W, focal), poses[i_test], images[i_test])
+        test_psnr, test_psnr_v2 = eval_test_split(trainer, args, data['hwf'], *data['test'], near=near, far=far, ndc=data['ndc'])
         return test_psnr, test_psnr_v2, '', None
 
+    step_args = data['step_args']
+    step_args['raw_noise_std'] = args.raw_noise_std
     # the [TRAIN] line's psnr is of img2mse(rgb) alone (main.py:1377-1379)
-    return run_iterations(args, trainer, start, (best_psnr, best_psnr_step), weights_dir, log, draw=draw,
-                          after_step=lambda batch, loss_rgb: float(loss_rgb.item()), test_pass=test_pass,
-                          step_args=dict(raw_noise_std=args.raw_noise_std))
+    return run_iterations(args, trainer, start, (best_psnr, best_psnr_step), weights_dir, log, draw=data['draw'],
+                          after_step=lambda batch, loss_rgb: float(loss_rgb.item()), test_pass=test_pass, step_args=step_args)
 
 
 def main(argv=None):

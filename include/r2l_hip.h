@@ -584,6 +584,18 @@ int r2l_lpips(const r2l_lpips_ctx* l, const float* a_dev, const float* b_dev, in
 int nerf_train_raw2outputs_backward(const float* raw_dev, const float* z_dev, const float* rays_d_dev, const float* noise_dev, int n,
                                     int S, int white_bkgd, const float* g_rgb_map_dev, float* g_raw_dev, void* stream);
 
+/* A step's rays of the reference's use_batching loop (main.py:1137-1162, 1199-1210) without its ray bank: ray k of the step is pixel
+ * order_dev[k] = image * H * W + row * W + column (int64, device; the caller's permutation already offset to the step's window) of
+ * images_dev uint8 [n_img, H, W, 3] under poses_dev float32 [n_img, 3, 4].  Four contiguous [rows, 3] float32 outputs, the layout
+ * the trainer reads: rays_o / rays_d are r2l_rays_from_images' (three channels, full resolution) and, with ndc != 0, nerf_ndc_rays
+ * (H, W, focal, near_) of them, bit for bit; viewdirs (may be NULL) is rays_d / ||rays_d|| of the WORLD direction in either mode
+ * (main.py:148-162); target is bytes / 255.  An index outside [0, n_img * H * W) gives NaN rows; rows = 0 launches nothing.  One
+ * thread per ray, plain coalesced stores, no atomics: the same inputs give the same bits.  poses and the outputs 4-byte aligned,
+ * order 8-byte aligned. */
+int nerf_train_batch_rays(const unsigned char* images_dev, int n_img, int H, int W, const float* poses_dev, double focal,
+                          const long long* order_dev, long long rows, int ndc, float near_, float* rays_o_dev, float* rays_d_dev,
+                          float* viewdirs_dev, float* target_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
