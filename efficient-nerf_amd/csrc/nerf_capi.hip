@@ -526,6 +526,9 @@ int nerf_load_weights(nerf_ctx* c, int which, const float* const* tensors, int n
     if (which != 0 && which != 1) return r2l_set_error(R2L_EINVAL, "which=%d (0 coarse, 1 fine)", which);
     if (n_tensors != 24) return r2l_set_error(R2L_EINVAL, "expected 24 tensors (NeRF D=8 W=256 use_viewdirs), got %d", n_tensors);
     PackedNet& net = c->net[which];
+    // from here on this network's old weights are gone: a load that is refused below leaves it unloaded (the other network is not
+    // touched), and every launch that needs it refuses with R2L_ESTATE until a load succeeds
+    net.loaded = false;
     net.host_w.clear();
     for (int i = 0; i < 24; ++i) {
         if (!tensors[i]) return r2l_set_error(R2L_EINVAL, "tensor %d is NULL", i);
@@ -548,7 +551,9 @@ int nerf_load_weights(nerf_ctx* c, int which, const float* const* tensors, int n
     int rc = build_net(c, net, c->mode_net[which]);
     if (rc) return rc;
     net.loaded = true;
-    return ensure_alpha_img(c);
+    rc = ensure_alpha_img(c);       // (packs from loaded networks only)
+    if (rc) net.loaded = false;
+    return rc;
 }
 
 int nerf_set_skip_rgb0(nerf_ctx* c, int on) {
@@ -567,14 +572,17 @@ int nerf_set_precision_pair(nerf_ctx* c, int coarse_mode, int fine_mode) {
     if (!c) return r2l_set_error(R2L_EINVAL, "NULL ctx");
     if (!mode_ok(coarse_mode) || !mode_ok(fine_mode)) return r2l_set_error(R2L_EINVAL, "bad precision_mode %d / %d", coarse_mode, fine_mode);
     const int modes[2] = {coarse_mode, fine_mode};
+    // both images first, then both modes: a build that is refused (weights the chain cannot pack) leaves the pair as it was (an image
+    // built for the other network stays cached for its mode; it is what a later switch would build)
     for (int which = 0; which < 2; ++which) {
         PackedNet& n = c->net[which];
         if (n.loaded && !n.d_img[modes[which]]) {
             int rc = build_net(c, n, modes[which]);
             if (rc) return rc;
         }
-        c->mode_net[which] = modes[which];
     }
+    c->mode_net[0] = coarse_mode;
+    c->mode_net[1] = fine_mode;
     c->mode = fine_mode;
     return ensure_alpha_img(c);
 }

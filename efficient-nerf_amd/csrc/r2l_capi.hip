@@ -373,12 +373,12 @@ static int build_image(r2l_ctx* c, int mode) {
                 for (int f = 0; f < 256; ++f) o[65536 + f] = auxb[f] / c->act_scale;
             }
             if (c->d_wcal) (void)hipFree(c->d_wcal);
-            if (c->d_stats) (void)hipFree(c->d_stats);
             c->d_wcal = nullptr;
-            c->d_stats = nullptr;
             eb = hipMalloc((void**)&c->d_wcal, wc.size() * sizeof(float));
             if (eb == hipSuccess) eb = hipMemcpy(c->d_wcal, wc.data(), wc.size() * sizeof(float), hipMemcpyHostToDevice);
-            if (eb == hipSuccess) eb = hipMalloc((void**)&c->d_stats, (size_t)(2 * c->n_block + 1) * sizeof(unsigned));
+            // the maxima of an open measurement (calib_started) live in d_stats: a mode change in between re-packs the streams but must
+            // keep them.  2 n_block + 1 words, n_block is fixed for the life of the context: allocated once
+            if (eb == hipSuccess && !c->d_stats) eb = hipMalloc((void**)&c->d_stats, (size_t)(2 * c->n_block + 1) * sizeof(unsigned));
             if (eb != hipSuccess) return r2l_set_error(R2L_EHIP, "calibration operands: %s", hipGetErrorString(eb));
         }
         // range tracking words; the h0 buffer of the context's own frame: nothing is allocated inside a render of <= H x W rays
@@ -719,6 +719,9 @@ int r2l_load_weights(r2l_ctx* c, const float* const* tensors, int n_tensors) {
     if (n_tensors != expect)
         return r2l_set_error(R2L_EINVAL, "expected %d tensors (head, %d ResMLP blocks x 4, tail), got %d", expect,
                              c->n_block, n_tensors);
+    // from here on the old weights are gone: a load that is refused below (a NULL tensor, weights the mode cannot pack) leaves the
+    // context unloaded, and every launch refuses with R2L_ESTATE until a load succeeds
+    c->loaded = false;
     c->host_w.clear();
     for (int i = 0; i < n_tensors; ++i) {
         size_t n;

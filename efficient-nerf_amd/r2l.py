@@ -180,13 +180,19 @@ class R2LEngine:
                 for k in (f'body.{i}.body.2.weight', f'body.{i}.body.2.bias'):
                     sd[k] = sd[k].detach().to('cpu', torch.float32) * self.res_scale
         keep, arr = _lib.host_ptrs([sd[n] for n in names])
-        with torch.cuda.device(self.device):
-            check(lib().r2l_load_weights(self._ctx, arr, len(keep)))
-        self._loaded = True
-        self._watch_state = {n: sd[n] for n in names}     # references, not copies: the three-pass watch context loads the same tensors
+        # a load the library refuses (weights the mode cannot pack) leaves the context unloaded (include/r2l_hip.h): so does this side, and
+        # the watch context, which holds the previous weights, goes with them
+        self._loaded = False
+        self._watch_state = None
         if getattr(self, '_watch_eng', None) is not None:
             self._watch_eng.close()
         self._watch_eng = None
+        with torch.cuda.device(self.device):
+            check(lib().r2l_load_weights(self._ctx, arr, len(keep)))
+        self._loaded = True
+        # a snapshot (float32 CPU clones, 23 MB for the 88-layer student), not references: the watch context is built lazily, and the caller
+        # may have changed or freed its tensors by then
+        self._watch_state = {n: t.clone() for n, t in zip(names, keep)}
         return self
 
     def set_precision(self, precision):

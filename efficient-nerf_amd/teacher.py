@@ -251,7 +251,9 @@ class NeRFEngine:
         """The `.tar`'s 'network_fn_state_dict' / 'network_fine_state_dict' (main.py:1516-1542)."""
         self._load(0, network_fn_state_dict)
         self._load(1, network_fine_state_dict)
-        self._fine_state = network_fine_state_dict        # a reference: rebalance_fine re-packs the fine network from it
+        # a snapshot (float32 CPU clones, 2.4 MB), not a reference: rebalance_fine re-packs the fine network from it, by which time the caller
+        # may have changed its tensors
+        self._fine_state = {k: v.detach().to('cpu', torch.float32).clone() for k, v in network_fine_state_dict.items()}
         self.fine_shifts = None
         return self
 

@@ -147,7 +147,10 @@ void r2l_destroy(r2l_ctx* ctx);
 /* tensors: 4 + 4*n_block HOST pointers in state_dict order:
  *   head.0.weight[256,1008], head.0.bias[256],
  *   body.{i}.body.0.weight[256,256], .bias[256], body.{i}.body.2.weight, .bias  (i < n_block),
- *   tail.0.weight[3,256], tail.0.bias[3]                                            */
+ *   tail.0.weight[3,256], tail.0.bias[3]
+ * May be called again on a live context.  A load that is refused (weights the current mode cannot pack, a NULL tensor) leaves the
+ * context unloaded: renders and r2l_set_act_exponents return R2L_ESTATE until a load succeeds.  A HIP graph captured before a
+ * reload holds pointers to the freed weight images; replaying it afterwards is the caller's error.                             */
 int r2l_load_weights(r2l_ctx* ctx, const float* const* tensors, int n_tensors);
 int r2l_set_precision(r2l_ctx* ctx, int precision_mode);
 /* R2L_PREC_FP16_SPLIT / _SPLIT8: the number of leading blocks in three passes = first block of the bf6 / e4m3 part, 0 .. n_block (takes
@@ -295,13 +298,16 @@ int nerf_create(nerf_ctx** out, int H, int W, double focal, float near_, float f
 void nerf_destroy(nerf_ctx* ctx);
 /* which: 0 = network_fn (coarse), 1 = network_fine.  tensors: 24 HOST pointers in
  * state_dict order: pts_linears.{0..7}.{weight,bias}, views_linears.0.{weight,bias},
- * feature_linear.{weight,bias}, alpha_linear.{weight,bias}, rgb_linear.{weight,bias}. */
+ * feature_linear.{weight,bias}, alpha_linear.{weight,bias}, rgb_linear.{weight,bias}.
+ * A load that is refused leaves THAT network unloaded (the other one is not touched): renders return R2L_ESTATE until it is
+ * loaded again. */
 int nerf_load_weights(nerf_ctx* ctx, int which, const float* const* tensors, int n_tensors);
 int nerf_set_precision(nerf_ctx* ctx, int precision_mode);
 /* one mode per network: coarse_mode for network_fn's launches, fine_mode for network_fine's (main.py:700-741).  The fine samples
  * are drawn from the coarse pass's weights (sample_pdf, helpers:283-330): on rays that graze an object those weights are ~0 and
  * the pdf is decided by differences at the 1e-4 level, so a trained teacher needs the coarse pass at fp32 grade (FP16X3) whatever
- * the fine pass runs in (profiles/r05_trained_like.txt). */
+ * the fine pass runs in (profiles/r05_trained_like.txt).  All or nothing: when either network's image for its new mode
+ * cannot be built, both networks keep the modes they had. */
 int nerf_set_precision_pair(nerf_ctx* ctx, int coarse_mode, int fine_mode);
 /* on != 0: for callers that drop render()'s extras, as the reference's own do (main.py:277-282, utils/create_data.py:824-831) -- the render
  * pipeline (nerf_render / nerf_render_rays[_ex]) leaves out work whose results only the extras rgb0 / raw would show:
