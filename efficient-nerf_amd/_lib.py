@@ -130,6 +130,7 @@ SIGNATURES = {
     'r2l_rays_from_images': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_double, C.c_int, _vp, C.c_longlong, _vp, _vp]),
     # rays for online distillation (csrc/r2l_online.hip)
     'r2l_rand_rays': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_ulonglong, C.c_longlong, C.c_longlong, _vp, _vp, _vp, _vp]),
+    'r2l_llff_rand_poses': (C.c_int, [_vp, C.c_int, C.c_int, _vp, C.c_double, _vp, _vp, _vp]),
     # FLIP (csrc/r2l_flip.hip)
     'r2l_flip_workspace_floats': (C.c_longlong, [C.c_int, C.c_int, C.c_double]),
     'r2l_flip': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_double,

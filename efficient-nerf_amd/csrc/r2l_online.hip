@@ -9,12 +9,17 @@
 //           and roundings of r2l_rays_from_images_kernel / nerf_get_rays_kernel: d = ((i - W/2) / focal, -(j - H/2) / focal, -1)
 //           rotated by the pose, the three products added in x, y, z order; the origin is the pose's last column
 // The output is a pure function of the arguments: no atomics, no generator state, nothing read back.
+// On an LLFF scene the poses themselves are built on the device first (r2l_llff_rand_poses_kernel below, one thread per pose, from
+// the step's uniform draws), so that a step's host work is one RandomState.rand call and its upload.
 // Store shape: a thread writes its own two 12-byte rows with three dword stores each, adjacent threads to adjacent rows, so a
 // wave's three store instructions together cover 768 contiguous bytes and the L2 merges them into whole lines.  Staging the rows
 // in LDS and writing coalesced runs was worth 6 % on r2l_rays_from_images' 576 MB (DESIGN, "Converting real images"); a step's
 // launch here writes 2.6 MB (81,920 rays x 32 bytes with the pixel indices) and is paced by the launch, not the stores.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
+
+#include <cmath>
 
 #include "../../include/r2l_hip.h"
 #include "r2l_host_util.h"
@@ -65,6 +70,66 @@ __global__ void __launch_bounds__(256) r2l_rand_rays_kernel(const float* __restr
     if (pixel) pixel[k] = pix;
 }
 
+// The poses of an LLFF step (llff.pose_in_boxes, the reference's get_rand_pose_v2 with its draws given): a position and a viewing
+// axis drawn in the two widened boxes of the scene, both carried through the average pose M (the translation is added to the
+// viewing axis too, as the reference does), then view_matrix.  box: M row-major [12], up [3], the position box left [3], right [3],
+// the viewing-axis box left [3], right [3] (llff.pose_box).  One thread builds one pose in binary64, one rounding per operation in
+// the order written here, and rounds the twelve entries to float32 once; a zero-length vector gives NaN rows, as numpy does.
+struct LLFFPoseBox {
+    double m[12], up[3], o_left[3], o_right[3], d_left[3], d_right[3];
+};
+static_assert(sizeof(LLFFPoseBox) == 27 * sizeof(double), "LLFFPoseBox is the 27 doubles of llff.pose_box");
+
+__device__ __forceinline__ void llff_normalise(double* v) {
+    const double n = __dsqrt_rn(__dadd_rn(__dadd_rn(__dmul_rn(v[0], v[0]), __dmul_rn(v[1], v[1])), __dmul_rn(v[2], v[2])));
+#pragma unroll
+    for (int r = 0; r < 3; ++r) v[r] = __ddiv_rn(v[r], n);
+}
+
+__device__ __forceinline__ void llff_cross(const double* a, const double* b, double* out) {
+    out[0] = __dsub_rn(__dmul_rn(a[1], b[2]), __dmul_rn(a[2], b[1]));
+    out[1] = __dsub_rn(__dmul_rn(a[2], b[0]), __dmul_rn(a[0], b[2]));
+    out[2] = __dsub_rn(__dmul_rn(a[0], b[1]), __dmul_rn(a[1], b[0]));
+}
+
+// M[:3, :4] . (p, 1), the three products added left to right and the translation last
+__device__ __forceinline__ void llff_through_pose(const double* m, const double* p, double* out) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+        out[r] = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(m[4 * r + 0], p[0]), __dmul_rn(m[4 * r + 1], p[1])), __dmul_rn(m[4 * r + 2], p[2])),
+                           m[4 * r + 3]);
+}
+
+__global__ void __launch_bounds__(256) r2l_llff_rand_poses_kernel(const double* __restrict__ u, int n_pose, int n_u, LLFFPoseBox box,
+                                                                   double focal, float* __restrict__ poses, float* __restrict__ focals) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_pose) return;
+    const double* __restrict__ uk = u + (size_t)k * n_u;
+    double po[3], pd[3], c[3], v0[3], v1[3], v2[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        po[r] = __dadd_rn(__dmul_rn(uk[r], __dsub_rn(box.o_right[r], box.o_left[r])), box.o_left[r]);
+        pd[r] = __dadd_rn(__dmul_rn(uk[3 + r], __dsub_rn(box.d_right[r], box.d_left[r])), box.d_left[r]);
+    }
+    llff_through_pose(box.m, po, c);
+    llff_through_pose(box.m, pd, v2);
+    llff_normalise(v2);                                  // pose_in_boxes' _normalize(z) ...
+    llff_normalise(v2);                                  // ... and view_matrix's own
+    llff_cross(box.up, v2, v0);
+    llff_normalise(v0);
+    llff_cross(v2, v0, v1);
+    llff_normalise(v1);
+    float* __restrict__ p = poses + (size_t)k * 12;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        p[4 * r + 0] = (float)v0[r];
+        p[4 * r + 1] = (float)v1[r];
+        p[4 * r + 2] = (float)v2[r];
+        p[4 * r + 3] = (float)c[r];
+    }
+    focals[k] = (float)(n_u == 7 ? __dmul_rn(focal, __dadd_rn(uk[6], 1.0)) : focal);
+}
+
 }  // namespace
 
 extern "C" {
@@ -89,6 +154,33 @@ int r2l_rand_rays(const float* poses_dev, const float* focal_dev, int n_pose, in
                        (uint32_t)(st >> 32), n, rays_o_dev, rays_d_dev, pixel_dev);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "r2l_rand_rays launch: %s", hipGetErrorString(e));
+    return R2L_OK;
+}
+
+int r2l_llff_rand_poses(const double* u_dev, int n_pose, int n_u, const double* box_host, double focal, float* poses_dev, float* focal_dev,
+                        void* stream) {
+    if (!u_dev || !box_host || !poses_dev || !focal_dev)
+        return r2l_set_error(R2L_EINVAL, "r2l_llff_rand_poses: u / box / poses / focal must not be NULL");
+    if (n_pose < 1) return r2l_set_error(R2L_EINVAL, "r2l_llff_rand_poses: n_pose = %d, at least one pose", n_pose);
+    if (n_u != 6 && n_u != 7)
+        return r2l_set_error(R2L_EINVAL, "r2l_llff_rand_poses: n_u = %d draws per pose, 7 (with the focal scale) or 6", n_u);
+    if (((uintptr_t)u_dev & 7) || ((uintptr_t)poses_dev & 3) || ((uintptr_t)focal_dev & 3))
+        return r2l_set_error(R2L_EINVAL, "r2l_llff_rand_poses: u must be 8-byte aligned, poses / focal 4-byte aligned");
+    if (!std::isfinite(focal) || !(focal > 0)) return r2l_set_error(R2L_EINVAL, "r2l_llff_rand_poses: focal = %g is not finite and positive", focal);
+    LLFFPoseBox box;
+    memcpy(&box, box_host, sizeof(box));
+    for (int i = 0; i < 27; ++i)
+        if (!std::isfinite(box_host[i])) return r2l_set_error(R2L_EINVAL, "r2l_llff_rand_poses: box entry %d = %g is not finite", i, box_host[i]);
+    for (int r = 0; r < 3; ++r)
+        if (!(box.o_right[r] > box.o_left[r]) || !(box.d_right[r] > box.d_left[r]))
+            return r2l_set_error(R2L_EINVAL, "r2l_llff_rand_poses: axis %d of a box is empty (position [%g, %g], viewing axis [%g, %g]; right must "
+                                 "exceed left)", r, box.o_left[r], box.o_right[r], box.d_left[r], box.d_right[r]);
+    int rc = r2l_require_gfx950(nullptr);
+    if (rc) return rc;
+    hipLaunchKernelGGL(r2l_llff_rand_poses_kernel, dim3((unsigned)(((long long)n_pose + 255) / 256)), dim3(256), 0, (hipStream_t)stream, u_dev, n_pose, n_u,
+                       box, focal, poses_dev, focal_dev);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "r2l_llff_rand_poses launch: %s", hipGetErrorString(e));
     return R2L_OK;
 }
 

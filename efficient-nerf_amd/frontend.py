@@ -79,7 +79,7 @@ FLAGS = [
     ('--i_print', dict(type=int, default=100)), ('--i_weights', dict(type=int, default=10000)), ('--resume', dict(action=_BOOL)),
     ('--num_workers', dict(type=int, default=8)),
     # online distillation (online.py): the teacher renders every step's rays on the device instead of --datadir_kd's shards.  --teacher_config:
-    # the teacher's own flags (default: lego.txt beside --config); --kd_online_poses random poses are mixed into a step (100: one save group of
+    # the teacher's own flags (default: lego.txt beside --config, on a mounted LLFF scene <the scene's folder>.txt); --kd_online_poses random poses are mixed into a step (100: one save group of
     # create_data rand), drawn from (--kd_online_seed, step); the teacher's mode is spot-checked every --kd_online_watch steps (0: never); a
     # step carries --N_rand x --kd_online_split rays
     ('--kd_online', dict(action=_BOOL)), ('--teacher_ckpt', dict(type=str, default='')), ('--teacher_config', dict(type=str, default='')),

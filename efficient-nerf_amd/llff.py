@@ -104,6 +104,18 @@ def pose_in_boxes(state, uo, ud, scale=1.1):
     return np.concatenate([view_matrix(_normalize(z), state.up, c), c2w[:, 4:5]], 1).astype(np.float32)
 
 
+def pose_box(state, scale=1.1):
+    """What pose_in_boxes reads of the state, as the 27 float64 r2l_llff_rand_poses takes (csrc/r2l_online.hip builds the poses of an
+    online step from it on the device): the average pose c2w[:3, :4] row-major (12), up (3), then left [3], right [3] of the
+    position box and of the viewing-axis box, each axis _scaled_range's own values in the state's dtype, widened to float64"""
+    sides = []
+    for mins, maxs in state.boxes():
+        ranges = [_scaled_range(mins[a], maxs[a], scale) for a in range(3)]
+        sides += [[r[0] for r in ranges], [r[1] for r in ranges]]
+    return np.concatenate([np.asarray(state.c2w[:3, :4], dtype=np.float64).ravel(), np.asarray(state.up, dtype=np.float64).ravel(),
+                           np.asarray(sides, dtype=np.float64).ravel()])
+
+
 def rand_pose(state, rs, scale=1.1):
     """get_rand_pose_v2 (load_llff.py:187-218) on the generator `rs` (an np.random.RandomState): six rand() draws in the reference's
     order -- position x, y, z, then viewing axis x, y, z"""

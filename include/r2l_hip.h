@@ -537,6 +537,20 @@ int r2l_rays_from_images(const unsigned char* images_dev, int n_img, int H0, int
 int r2l_rand_rays(const float* poses_dev, const float* focal_dev, int n_pose, int H, int W, unsigned long long seed, long long step,
                   long long n, float* rays_o_dev, float* rays_d_dev, long long* pixel_dev, void* stream);
 
+/* The random poses of an LLFF step, built on the device (host mirror: llff.pose_in_boxes, the reference's get_rand_pose_v2,
+ * dataset/load_llff.py:187-236, with its draws given).  u_dev: float64 [n_pose, n_u] uniform draws in [0, 1), n_u = 7 or 6: the
+ * position in its box (x, y, z), the viewing axis in its box (x, y, z) and, with n_u = 7, the focal scale u + 1 drawn after each
+ * pose.  box_host: 27 doubles in HOST memory, passed to the kernel by value (llff.pose_box): the average pose c2w[:3, :4] row-major
+ * (12), up (3), the widened position box left [3], right [3], the widened viewing-axis box left [3], right [3].  Pose k:
+ * p = u (right - left) + left per axis; position and viewing axis are c2w . (p, 1), the translation added to both; the axis is
+ * normalised, then view_matrix(axis, up, position).  poses_dev [n_pose, 3, 4] and focal_dev [n_pose] = focal (u6 + 1), or focal
+ * with n_u = 6, are float32, ready for r2l_rand_rays.  Computed in binary64, one rounding per operation, each entry rounded to
+ * float32 once; one thread per pose, plain stores, no atomics: the output is a function of the arguments alone.  A zero-length
+ * vector gives NaN rows.  R2L_EINVAL: a NULL pointer, n_pose < 1, another n_u, a misaligned pointer, a focal that is not finite and
+ * positive, a box entry that is not finite, a box with right <= left. */
+int r2l_llff_rand_poses(const double* u_dev, int n_pose, int n_u, const double* box_host, double focal, float* poses_dev, float* focal_dev,
+                        void* stream);
+
 /* ---- FLIP of image pairs (csrc/r2l_flip.hip; host side: efficient-nerf_amd/metrics.py flip, flip_taps.py) ----
  * FLIP.compute_flip(a, b, pixels_per_degree) of utils/flip_loss.py:70-130, the TestFLIP of the reference's [TEST] lines, on
  * v = mul * (x - lo) + add of each image (three roundings, applied first; (0, 1, 0) is the identity, exactly): sRGB clamped to
