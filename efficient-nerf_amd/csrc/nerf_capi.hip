@@ -16,13 +16,23 @@
 namespace {
 
 struct PackedNet {
-    char* d_img[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // [precision mode]
-    float inv_scale[8][NERF_N_SCALES];
-    char* d_img_alpha = nullptr;             // the three-pass stream without the view branch (coarse network, nerf_set_skip_rgb0)
-    char* d_img_exit = nullptr;              // the fine network's stream with the second exit behind the density (fp16x3_asm or fp16_mix), and
-    int exit_mode = -1;                      // the mode it was packed for
+    DevBuf<char> d_img[8];                   // [precision mode]
+    float inv_scale[8][NERF_N_SCALES] = {};
+    DevBuf<char> d_img_alpha;                // the three-pass stream without the view branch (coarse network, nerf_set_skip_rgb0)
+    DevBuf<char> d_img_exit;                 // the fine network's stream with the second exit behind the density (fp16x3_asm or fp16_mix), and
+    int exit_mode = -1;                      // the mode it was packed for: -1 exactly when there is none (drop_exit, ensure_alpha_img)
     std::vector<std::vector<float>> host_w;  // 24 tensors, state_dict order
     bool loaded = false;
+
+    void drop_exit() {
+        d_img_exit.release();
+        exit_mode = -1;
+    }
+    void drop_images() {                     // everything packed from host_w
+        for (auto& img : d_img) img.release();
+        d_img_alpha.release();
+        drop_exit();
+    }
 };
 
 // state_dict order (model/nerf_raybased.py:357-375)
@@ -33,16 +43,8 @@ const size_t kTensorNumel[24] = {
     256 * 319, 256, 256 * 256, 256, 256 * 256, 256,                                    // pts_linears 5..7
     128 * 283, 128, 256 * 256, 256, 256, 1, 3 * 128, 3};
 
-int np_of(int mode) { return mode == R2L_PREC_FP16X1 ? 1 : 2; }
 bool mode_ok(int mode) {
     return mode == R2L_PREC_FP16X3 || mode == R2L_PREC_FP16X1 || mode == R2L_PREC_FP16_FP8 || mode == R2L_PREC_FP16X3_ASM || mode == R2L_PREC_FP16_MIX;
-}
-
-void put_frag(char* chunk, int np, int frag, int lane, int j, float v) {
-    _Float16 hi, lo;
-    r2l_split_f16(v, &hi, np == 2 ? &lo : nullptr);
-    reinterpret_cast<_Float16*>(chunk + (size_t)(frag * np + 0) * R2L_FRAG_BYTES + lane * 16)[j] = hi;
-    if (np == 2) reinterpret_cast<_Float16*>(chunk + (size_t)(frag * np + 1) * R2L_FRAG_BYTES + lane * 16)[j] = lo;
 }
 
 // One layer of the fragment stream: RT row tiles (16 outputs) x KS k-steps (32 inputs).
@@ -301,8 +303,9 @@ int pack_chain(const std::vector<std::vector<float>>& w, float Sa, std::vector<c
 
 }  // namespace
 
+// Every member has an initialiser or owns what it holds: `delete` frees all of it.
 struct nerf_ctx {
-    int H, W, N_samples, N_importance, white_bkgd, mode, n_cu;
+    int H = 0, W = 0, N_samples = 0, N_importance = 0, white_bkgd = 0, mode = 0, n_cu = 0;
     int mode_net[2] = {0, 0};   // precision of the coarse / the fine network's MLP launches (nerf_set_precision: both; nerf_set_precision_pair)
     int ndc = 0;            // render() projects the rays to NDC first (main.py:160-162)
     bool skip_rgb0 = false;    // nerf_set_skip_rgb0: the coarse pass of the render pipeline without its view branch when it runs fp16x3_asm
@@ -310,55 +313,39 @@ struct nerf_ctx {
     int x1_col_tiles = 4;      // nerf_debug_set_x1_col_tiles: 16-point column tiles per wave of the fp16-only chain (3 or 2 for the A/B)
     bool x1_stream_embed = true;   // nerf_debug_set_x1_stream_embed: the four-tile chain with its embedding in the stream (nerf_chain_emb_kernel)
     float ndc_near = 1.0f;
-    double focal;
-    float near_, far_, act_scale;
+    double focal = 0;
+    float near_ = 0, far_ = 0, act_scale = 16.0f;
     std::vector<float> z_coarse, u;  // host copies
-    float *d_zc = nullptr, *d_zmid = nullptr, *d_u = nullptr;
-    float* d_zsort = nullptr;  // z_samples sorted (random uniforms only)
+    DevBuf<float> d_zc, d_zmid, d_u;
     PackedNet net[2];
-    // per-call temporaries, grown on demand (sized for `cap` rays)
+    // per-call temporaries, grown on demand (all sized for `cap` rays: ensure_tmp)
     int cap = 0;
-    float *d_rays_o = nullptr, *d_rays_d = nullptr, *d_raw0 = nullptr, *d_w0 = nullptr, *d_zs = nullptr,
-          *d_zall = nullptr, *d_raw = nullptr, *d_rgb0 = nullptr, *d_disp0 = nullptr, *d_acc0 = nullptr,
-          *d_ndc_o = nullptr, *d_ndc_d = nullptr, *d_vdir = nullptr;
-    // HIP-event timing of the MLP launches (nerf_timing_enable / nerf_kernel_time_ms), on the stream they are launched on
-    bool timing = false;
-    std::vector<hipEvent_t> ev;   // pairs
-    int ev_used = 0;
+    DevBuf<float> d_rays_o, d_rays_d, d_raw0, d_w0, d_zs, d_zall, d_raw, d_rgb0, d_disp0, d_acc0, d_ndc_o, d_ndc_d, d_vdir;
+    DevBuf<float> d_zsort;     // z_samples sorted (random uniforms only)
+    EventTimer timer;          // brackets the MLP launches (nerf_timing_enable / nerf_kernel_time_ms), on the stream they are launched on
 };
 
 static int ensure_alpha_img(nerf_ctx* c);
 
-static void free_tmp(nerf_ctx* c) {
-    float** ps[] = {&c->d_rays_o, &c->d_rays_d, &c->d_raw0, &c->d_w0, &c->d_zs, &c->d_zall, &c->d_raw,
-                    &c->d_rgb0, &c->d_disp0, &c->d_acc0, &c->d_ndc_o, &c->d_ndc_d, &c->d_vdir, &c->d_zsort};
-    for (auto p : ps)
-        if (*p) {
-            (void)hipFree(*p);
-            *p = nullptr;
-        }
-    c->cap = 0;
-}
-
 static int ensure_tmp(nerf_ctx* c, int n) {
     if (n <= c->cap) return R2L_OK;
-    free_tmp(c);
     const int S0 = c->N_samples, S1 = c->N_samples + c->N_importance;
-    struct { float** p; size_t numel; } req[] = {
+    struct { DevBuf<float>* b; size_t numel; } req[] = {
         {&c->d_rays_o, (size_t)n * 3}, {&c->d_rays_d, (size_t)n * 3}, {&c->d_raw0, (size_t)n * S0 * 4},
         {&c->d_w0, (size_t)n * S0},    {&c->d_zs, (size_t)n * c->N_importance}, {&c->d_zall, (size_t)n * S1},
         {&c->d_raw, (size_t)n * S1 * 4}, {&c->d_rgb0, (size_t)n * 3}, {&c->d_disp0, (size_t)n}, {&c->d_acc0, (size_t)n},
         {&c->d_ndc_o, (size_t)n * 3}, {&c->d_ndc_d, (size_t)n * 3}, {&c->d_vdir, (size_t)n * 3},
         {&c->d_zsort, (size_t)n * c->N_importance}};
-    for (auto& r : req) {
-        hipError_t e = hipMalloc((void**)r.p, r.numel * sizeof(float));
-        if (e != hipSuccess) {
-            free_tmp(c);
-            return r2l_set_error(R2L_EHIP, "hipMalloc temporaries for %d rays: %s", n, hipGetErrorString(e));
-        }
-    }
-    c->cap = n;
-    return R2L_OK;
+    // every old one goes before the first new one comes: hundreds of MB, and the peak must not hold both sets
+    int rc = R2L_OK;
+    c->cap = 0;
+    for (auto& r : req) r.b->release();
+    for (auto& r : req)
+        if (rc == R2L_OK) rc = r.b->grow(r.numel, "ray temporaries");
+    for (auto& r : req)
+        if (rc) r.b->release();
+    if (rc == R2L_OK) c->cap = n;
+    return rc;
 }
 
 static int upload_sampling(nerf_ctx* c) {
@@ -369,16 +356,13 @@ static int upload_sampling(nerf_ctx* c) {
         volatile float m = .5f * s;
         zmid[i] = m;
     }
-    struct { float** d; const float* h; size_t n; } up[] = {
+    struct { DevBuf<float>* d; const float* h; size_t n; } up[] = {
         {&c->d_zc, c->z_coarse.data(), (size_t)S}, {&c->d_zmid, zmid.data(), (size_t)S - 1},
         {&c->d_u, c->u.data(), (size_t)c->N_importance}};
-    for (auto& x : up) {
-        if (!*x.d) {
-            hipError_t e = hipMalloc((void**)x.d, x.n * sizeof(float));
-            if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "hipMalloc: %s", hipGetErrorString(e));
-        }
-        hipError_t e = hipMemcpy(*x.d, x.h, x.n * sizeof(float), hipMemcpyHostToDevice);
-        if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "hipMemcpy: %s", hipGetErrorString(e));
+    for (auto& x : up) {      // in place after the first time: a captured render keeps reading the same addresses
+        int rc = x.d->grow(x.n, "sampling tables");
+        if (rc) return rc;
+        HIPCHK(hipMemcpy(x.d->get(), x.h, x.n * sizeof(float), hipMemcpyHostToDevice), "sampling tables");
     }
     return R2L_OK;
 }
@@ -402,14 +386,14 @@ int nerf_create(nerf_ctx** out, int H, int W, double focal, float near_, float f
     nerf_ctx* c = new nerf_ctx();
     c->H = H; c->W = W; c->focal = focal; c->near_ = near_; c->far_ = far_;
     c->N_samples = N_samples; c->N_importance = N_importance; c->white_bkgd = white_bkgd ? 1 : 0;
-    c->mode = c->mode_net[0] = c->mode_net[1] = precision_mode; c->n_cu = n_cu; c->act_scale = 16.0f;
+    c->mode = c->mode_net[0] = c->mode_net[1] = precision_mode; c->n_cu = n_cu;
     c->z_coarse.resize(N_samples);
     r2l_z_vals(N_samples, near_, far_, c->z_coarse.data());  // main.py:676-678
     c->u.resize(N_importance);
     r2l_linspace01(N_importance, c->u.data());               // helpers:293
     rc = upload_sampling(c);
     if (rc) {
-        nerf_destroy(c);
+        delete c;
         return rc;
     }
     *out = c;
@@ -417,20 +401,7 @@ int nerf_create(nerf_ctx** out, int H, int W, double focal, float near_, float f
 }
 
 void nerf_destroy(nerf_ctx* c) {
-    if (!c) return;
-    free_tmp(c);
-    for (auto& n : c->net)
-        for (int m = 0; m < 8; ++m)
-            if (n.d_img[m]) (void)hipFree(n.d_img[m]);
-    for (auto& n : c->net) {
-        if (n.d_img_alpha) (void)hipFree(n.d_img_alpha);
-        if (n.d_img_exit) (void)hipFree(n.d_img_exit);
-    }
-    if (c->d_zc) (void)hipFree(c->d_zc);
-    if (c->d_zmid) (void)hipFree(c->d_zmid);
-    if (c->d_u) (void)hipFree(c->d_u);
-    for (auto& e : c->ev) (void)hipEventDestroy(e);
-    delete c;
+    if (c) delete c;
 }
 
 int nerf_set_sampling(nerf_ctx* c, const float* z_coarse_host, int n_z, const float* u_host, int n_u) {
@@ -446,24 +417,16 @@ int nerf_set_sampling(nerf_ctx* c, const float* z_coarse_host, int n_z, const fl
     return upload_sampling(c);
 }
 
-static int upload_img(PackedNet& net, int mode, const std::vector<char>& img) {
-    if (net.d_img[mode]) {
-        (void)hipFree(net.d_img[mode]);
-        net.d_img[mode] = nullptr;
-    }
-    hipError_t e = hipMalloc((void**)&net.d_img[mode], img.size());
-    if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "hipMalloc image: %s", hipGetErrorString(e));
-    e = hipMemcpy(net.d_img[mode], img.data(), img.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "hipMemcpy image: %s", hipGetErrorString(e));
-    return R2L_OK;
+// the network's weights as the layer chain's stream of format `fmt`, packed and put into `dst`; weights the format refuses leave dst as it was
+static int upload_chain(const nerf_ctx* c, const PackedNet& net, NerfChainFmt fmt, DevBuf<char>& dst, const char* what) {
+    std::vector<char> img;
+    int rc = pack_chain(net.host_w, c->act_scale, img, kNerfChain[fmt]);
+    return rc ? rc : dst.upload(img.data(), img.size(), what);
 }
 
 static int build_net(nerf_ctx* c, PackedNet& net, int mode) {
-    if (mode == R2L_PREC_FP16_FP8 || mode == R2L_PREC_FP16X1 || mode == R2L_PREC_FP16X3_ASM || mode == R2L_PREC_FP16_MIX) {  // the layer chain's own streams
-        std::vector<char> img;
-        int rc = pack_chain(net.host_w, c->act_scale, img, kNerfChain[chain_fmt_of_mode(mode)]);
-        return rc ? rc : upload_img(net, mode, img);
-    }
+    if (mode == R2L_PREC_FP16_FP8 || mode == R2L_PREC_FP16X1 || mode == R2L_PREC_FP16X3_ASM || mode == R2L_PREC_FP16_MIX)  // the layer chain's own streams
+        return upload_chain(c, net, chain_fmt_of_mode(mode), net.d_img[mode], "image");
     const int np = np_of(mode);
     const int CH = r2l_chunk_bytes(np);
     std::vector<char> img((size_t)NERF_CHUNKS * CH, 0);
@@ -518,7 +481,7 @@ static int build_net(nerf_ctx* c, PackedNet& net, int mode) {
     // RGB
     pack_layer(img, np, NERF_F0_RGB, 4, 1, Sa, mat(T_RGB_W, 128, 3), kap, vec(T_RGB_B, 3),
                r2l_pow2_scale(w[T_RGB_W].data(), w[T_RGB_W].size()), &inv[10]);
-    return upload_img(net, mode, img);
+    return net.d_img[mode].upload(img.data(), img.size(), "image");
 }
 
 int nerf_load_weights(nerf_ctx* c, int which, const float* const* tensors, int n_tensors) {
@@ -534,20 +497,7 @@ int nerf_load_weights(nerf_ctx* c, int which, const float* const* tensors, int n
         if (!tensors[i]) return r2l_set_error(R2L_EINVAL, "tensor %d is NULL", i);
         net.host_w.emplace_back(tensors[i], tensors[i] + kTensorNumel[i]);
     }
-    for (int m = 0; m < 8; ++m)
-        if (net.d_img[m]) {
-            (void)hipFree(net.d_img[m]);
-            net.d_img[m] = nullptr;
-        }
-    if (net.d_img_alpha) {
-        (void)hipFree(net.d_img_alpha);
-        net.d_img_alpha = nullptr;
-    }
-    if (net.d_img_exit) {
-        (void)hipFree(net.d_img_exit);
-        net.d_img_exit = nullptr;
-        net.exit_mode = -1;
-    }
+    net.drop_images();
     int rc = build_net(c, net, c->mode_net[which]);
     if (rc) return rc;
     net.loaded = true;
@@ -593,27 +543,16 @@ static int ensure_alpha_img(nerf_ctx* c) {
         PackedNet& f = c->net[1];
         const int fm = c->mode_net[1];
         if (f.loaded && (fm == R2L_PREC_FP16X3_ASM || fm == R2L_PREC_FP16_MIX) && f.exit_mode != fm) {
-            std::vector<char> img;
-            int rc = pack_chain(f.host_w, c->act_scale, img, kNerfChain[fm == R2L_PREC_FP16_MIX ? NERF_FMT_MIXS : NERF_FMT_P3S]);
+            f.drop_exit();      // (of a mode the network has left: a return to it packs the same bytes again)
+            int rc = upload_chain(c, f, fm == R2L_PREC_FP16_MIX ? NERF_FMT_MIXS : NERF_FMT_P3S, f.d_img_exit,
+                                  "the fine network's stream with the second exit");
             if (rc) return rc;
-            if (f.d_img_exit) (void)hipFree(f.d_img_exit);
-            f.d_img_exit = nullptr;
-            f.exit_mode = -1;
-            hipError_t e = hipMalloc((void**)&f.d_img_exit, img.size());
-            if (e == hipSuccess) e = hipMemcpy(f.d_img_exit, img.data(), img.size(), hipMemcpyHostToDevice);
-            if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "the fine network's stream with the second exit: %s", hipGetErrorString(e));
             f.exit_mode = fm;
         }
     }
     PackedNet& n = c->net[0];
     if (!c->skip_rgb0 || !n.loaded || n.d_img_alpha || c->mode_net[0] != R2L_PREC_FP16X3_ASM) return R2L_OK;
-    std::vector<char> img;
-    int rc = pack_chain(n.host_w, c->act_scale, img, kNerfChain[NERF_FMT_P3A]);
-    if (rc) return rc;
-    hipError_t e = hipMalloc((void**)&n.d_img_alpha, img.size());
-    if (e == hipSuccess) e = hipMemcpy(n.d_img_alpha, img.data(), img.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "the coarse network's stream without its view branch: %s", hipGetErrorString(e));
-    return R2L_OK;
+    return upload_chain(c, n, NERF_FMT_P3A, n.d_img_alpha, "the coarse network's stream without its view branch");
 }
 
 static int run_mlp(nerf_ctx* c, int which, const float* rays_o, const float* rays_d, const float* z, int z_stride,
@@ -659,22 +598,10 @@ static int run_mlp(nerf_ctx* c, int which, const float* rays_o, const float* ray
     p.neg1 = -1.0f;
     memcpy(p.inv_scale, c->net[which].inv_scale[mode], sizeof p.inv_scale);
     const int grid = balanced_grid(p.n_tiles, c->n_cu);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->timing) {
-        if (c->ev_used + 2 > (int)c->ev.size())
-            for (int i = 0; i < 2; ++i) {
-                hipEvent_t ev;
-                hipError_t er = hipEventCreate(&ev);
-                if (er != hipSuccess) return r2l_set_error(R2L_EHIP, "hipEventCreate: %s", hipGetErrorString(er));
-                c->ev.push_back(ev);
-            }
-        e0 = c->ev[c->ev_used];
-        e1 = c->ev[c->ev_used + 1];
-        c->ev_used += 2;
-        (void)hipEventRecord(e0, s);
-    }
+    int rc = c->timer.start(s);
+    if (rc) return rc;
     hipError_t e = nerf_launch_mlp(p, mode, grid, s, x1_nc, stream_embed, alpha_only, second_exit);
-    if (c->timing) (void)hipEventRecord(e1, s);
+    c->timer.stop(s);
     if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "nerf_mlp launch: %s", hipGetErrorString(e));
     // a point or a direction with a NaN in its embedding: NaN into its raw, as the reference's networks give (the kernels' ReLU dropped it)
     e = nerf_launch_mark_nonfinite(p, ordered_rows, s);
@@ -684,31 +611,14 @@ static int run_mlp(nerf_ctx* c, int which, const float* rays_o, const float* ray
 
 int nerf_timing_enable(nerf_ctx* c, int on) {
     if (!c) return r2l_set_error(R2L_EINVAL, "NULL ctx");
-    c->timing = on != 0;
+    c->timer.on = on != 0;
     return R2L_OK;
 }
 
 int nerf_kernel_time_ms(nerf_ctx* c, double* total_ms, int* n_launches, int reset) {
     if (!c || !total_ms || !n_launches) return r2l_set_error(R2L_EINVAL, "NULL argument");
-    double tot = 0;
-    for (int i = 0; i + 1 < c->ev_used; i += 2) {
-        hipError_t e = hipEventSynchronize(c->ev[i + 1]);
-        float ms = 0;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]);
-        if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "event timing: %s", hipGetErrorString(e));
-        tot += ms;
-    }
-    *total_ms = tot;
-    *n_launches = c->ev_used / 2;
-    if (reset) c->ev_used = 0;
-    return R2L_OK;
+    return c->timer.total(total_ms, n_launches, reset);
 }
-
-#define HIPCHK(call, what)                                                                   \
-    do {                                                                                     \
-        hipError_t e_ = (call);                                                              \
-        if (e_ != hipSuccess) return r2l_set_error(R2L_EHIP, what ": %s", hipGetErrorString(e_)); \
-    } while (0)
 
 // Randomness of render_rays (training-time options of the reference; all null on the test path).  The caller draws
 // the numbers exactly as the reference does (torch.rand / the pytest numpy streams) and hands them over:

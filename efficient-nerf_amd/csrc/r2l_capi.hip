@@ -145,25 +145,26 @@ static unsigned char r2l_f_to_e4m3(double v) {
     return sgn | (unsigned char)(((E + 7) << 3) | (qn - 8));
 }
 
+#define R2L_N_MODES 7
+
+// Every member has an initialiser or owns what it holds: `new r2l_ctx` is a valid empty context and `delete` frees all of it.
 struct r2l_ctx {
-    int H, W, n_block, use_residual, mode;
-    double focal;
-    float near_, far_;
-    float z[16];
-    float act_scale;
-    int n_cu;
-    bool loaded;
+    int H = 0, W = 0, n_block = 0, use_residual = 0, mode = 0;
+    double focal = 0;
+    float near_ = 0, far_ = 0;
+    float z[16] = {};
+    float act_scale = 16.0f;
+    int n_cu = 0;
+    bool loaded = false;
     std::vector<std::vector<float>> host_w;  // state_dict order
-    char* d_img[7];                           // [mode] packed image (FP16_FP8: the 32 head chunks, hi|lo layout)
-    size_t img_bytes[7];
-    char* d_body;                             // split modes: body stream v3 (r2l_body.hip) | aux blocks | tail
+    DevBuf<char> d_img[R2L_N_MODES];          // [mode] packed image (FP16_FP8: the 32 head chunks, hi|lo layout)
+    DevBuf<char> d_body;                      // split modes: body stream v3 (r2l_body.hip) | aux blocks | tail
     int body_mode = -1;                       // ... of this mode (bf6 or e4m3 terms: chunk geometry and operand codes differ)
-    size_t body_bytes, aux_off, tail_off;
+    size_t aux_off = 0, tail_off = 0;
     // R2L_PREC_FP16_SPLIT / _SPLIT8: blocks [0, split_block) run on the three-pass stream d_body2, blocks [split_block, n_block) on d_body
-    // (bf6 / e4m3 terms)
-    char* d_body2 = nullptr;
-    size_t aux_split_off = 0;
-    size_t body2_bytes = 0, aux_off2 = 0, tail_off2 = 0;
+    // (bf6 / e4m3 terms); behind the stream, at aux_split_off: room for the aux blocks of a truncated launch
+    DevBuf<char> d_body2;
+    size_t aux_split_off = 0, aux_off2 = 0, tail_off2 = 0;
     int split_block = -1;                     // -1: n_block / 2 until r2l_set_split_block
     std::vector<int> act;                     // FP16_FP8: 2 n_block + 1 activation exponents (packed into the aux blocks)
     // activations as slopes (act(v) = max(v, s v): 0 relu, 0.01 LeakyReLU, 1 none): head, inside a block, behind a block.  The
@@ -174,31 +175,28 @@ struct r2l_ctx {
     int calib_pending = 0;                    // the next FP16_FP8 render derives them from its own head output (device side)
     int calib_started = 0;                    // maxima of earlier, smaller calls are in d_stats: the next measurement adds to them
     int calib_calls = 0;                      // thin calls the open measurement has seen (closed after R2L_CALIB_MAX_CALLS)
-    // range tracking (r2l_get_range_status), ONE allocation so that the host reads it with one copy:
+    // range tracking (r2l_get_range_status), ONE allocation (d_range owns it, the other two are views) so that the host reads it
+    // with one copy:
     // d_range[0] = max h0 of EVERY ray since the last reset (head launch), [1..3] spare;
     // d_gstats = d_range + 4: [2 n_block + 1] maxima of every operand set over every ray of the guarded body launches since
     // the last reset; d_exps = d_gstats + 2 n_block + 1: [2 n_block + 1] the activation exponents in use (what the aux blocks
     // hold, written beside them by the calibration kernels and by r2l_set_act_exponents)
-    unsigned* d_range = nullptr;
+    DevBuf<unsigned> d_range;
     unsigned* d_gstats = nullptr;
     int* d_exps = nullptr;
     int guard_period = R2L_GUARD_PERIOD_DEFAULT;
     long long n_body = 0, n_guarded = 0;      // FP16_FP8 body launches since the last reset / of them guarded
     long long n_since_load = 0;               // ... since r2l_load_weights (the guard's phase)
     hipStream_t last_stream = nullptr;        // stream of the newest render: the synchronous host copies wait for it
-    float* d_wcal = nullptr;                  // fp32 W1^T | b1' | W2^T per block for the calibration kernel
-    unsigned* d_stats = nullptr;
-    float* d_xa;                              // FP16_FP8: head output of one launch slice (1 KiB per ray)
-    float* d_xb;                              // body output: only the unfused form (no global skip, r2l_debug_set_fused_tail(0))
-    int x_tiles, xb_tiles;                    // capacity of d_xa / d_xb in ray tiles
-    float* d_scratch;
-    float* d_z;  // device copy of z
-    bool timing;
-    std::vector<hipEvent_t> ev;  // pairs
-    int ev_used;
+    DevBuf<float> d_wcal;                     // fp32 W1^T | b1' | W2^T per block for the calibration kernel
+    DevBuf<unsigned> d_stats;                 // maxima of an open measurement: 2 n_block + 1 words, allocated once per context
+    DevBuf<float> d_xa;                       // FP16_FP8: head output of one launch slice (1 KiB per ray)
+    DevBuf<float> d_xb;                       // body output: only the unfused form (no global skip, r2l_debug_set_fused_tail(0))
+    DevBuf<float> d_scratch;
+    DevBuf<float> d_z;                        // device copy of z
+    EventTimer timer;                         // brackets the dominant launch of a render (r2l_timing_enable)
 };
 
-static int np_of(int mode) { return mode == R2L_PREC_FP16X1 ? 1 : 2; }
 enum { R2L_STREAM_BF6 = 0, R2L_STREAM_E4M3 = 1, R2L_STREAM_BF6R = 2, R2L_STREAM_F16 = 3 };   // body stream layouts (pack_body_v3)
 static bool mode_ok(int mode) { return mode >= R2L_PREC_FP16X3 && mode <= R2L_PREC_FP16_SPLIT8; }
 // the split rungs: head + leading blocks in three passes, the rest with bf6 (SPLIT) or e4m3 (SPLIT8) terms
@@ -218,8 +216,6 @@ static int stream_of(int mode) {
     return e4m3_terms(mode) ? R2L_STREAM_E4M3 : mode == R2L_PREC_FP16X3_ASM ? R2L_STREAM_F16 :
            (R2L_BF6_CHUNK == 28672 ? R2L_STREAM_BF6 : R2L_STREAM_BF6R);
 }
-#define R2L_N_MODES 7
-
 
 #ifndef R2L_SLICE_TILES
 #define R2L_SLICE_TILES 8192   // FP16_FP8: ray tiles per head / body launch pair (1 KiB of h0 per ray)
@@ -250,67 +246,23 @@ int r2l_create(r2l_ctx** out, int H, int W, double focal, float near_, float far
     c->n_block = n_block;
     c->use_residual = use_residual ? 1 : 0;
     c->mode = precision_mode;
-    c->act_scale = 16.0f;
     c->n_cu = n_cu;
-    c->loaded = false;
-    for (int m = 0; m < R2L_N_MODES; ++m) {
-        c->d_img[m] = nullptr;
-        c->img_bytes[m] = 0;
-    }
-    c->d_body = nullptr;
-    c->body_bytes = c->aux_off = c->tail_off = 0;
-    c->d_xa = c->d_xb = nullptr;
-    c->x_tiles = c->xb_tiles = 0;
-    c->d_scratch = nullptr;
-    c->d_z = nullptr;
-    c->timing = false;
-    c->ev_used = 0;
     r2l_z_vals(R2L_NSAMPLE, near_, far_, c->z);
-    size_t scr = (size_t)n_cu * R2L_WAVES * 32 * 256 * sizeof(float);
-    hipError_t e = hipMalloc((void**)&c->d_scratch, scr);
-    if (e != hipSuccess) {
+    rc = c->d_scratch.grow((size_t)n_cu * R2L_WAVES * 32 * 256, "scratch");
+    if (rc == R2L_OK) rc = c->d_z.upload(c->z, R2L_NSAMPLE, "z_vals");
+    if (rc) {
         delete c;
-        return r2l_set_error(R2L_EHIP, "hipMalloc scratch: %s", hipGetErrorString(e));
-    }
-    e = hipMalloc((void**)&c->d_z, sizeof c->z);
-    if (e == hipSuccess) e = hipMemcpy(c->d_z, c->z, sizeof c->z, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        r2l_destroy(c);
-        return r2l_set_error(R2L_EHIP, "hipMalloc/hipMemcpy z_vals: %s", hipGetErrorString(e));
+        return rc;
     }
     *out = c;
     return R2L_OK;
 }
 
 void r2l_destroy(r2l_ctx* c) {
-    if (!c) return;
-    for (int m = 0; m < R2L_N_MODES; ++m)
-        if (c->d_img[m]) (void)hipFree(c->d_img[m]);
-    if (c->d_body) (void)hipFree(c->d_body);
-    if (c->d_body2) (void)hipFree(c->d_body2);
-    if (c->d_xa) (void)hipFree(c->d_xa);
-    if (c->d_xb) (void)hipFree(c->d_xb);
-    if (c->d_wcal) (void)hipFree(c->d_wcal);
-    if (c->d_stats) (void)hipFree(c->d_stats);
-    if (c->d_range) (void)hipFree(c->d_range);   // d_gstats, d_exps: the same allocation
-    if (c->d_scratch) (void)hipFree(c->d_scratch);
-    if (c->d_z) (void)hipFree(c->d_z);
-    for (auto& e : c->ev) (void)hipEventDestroy(e);
-    delete c;
+    if (c) delete c;
 }
 
 // ---- packing ---------------------------------------------------------------------------
-static void put_frag(char* chunk, int np, int frag, int lane, int j, float v) {
-    _Float16 hi, lo;
-    r2l_split_f16(v, &hi, np == 2 ? &lo : nullptr);
-    _Float16* ph = reinterpret_cast<_Float16*>(chunk + (size_t)(frag * np + 0) * R2L_FRAG_BYTES + lane * 16);
-    ph[j] = hi;
-    if (np == 2) {
-        _Float16* pl = reinterpret_cast<_Float16*>(chunk + (size_t)(frag * np + 1) * R2L_FRAG_BYTES + lane * 16);
-        pl[j] = lo;
-    }
-}
-
 static void pack_image_host(const r2l_ctx* c, int mode, std::vector<char>& img);
 static int ensure_x(r2l_ctx* c, int tiles, bool need_xb);
 static int pack_body_v3(const r2l_ctx* c, int e4m3, std::vector<char>& out, size_t* aux_off, size_t* tail_off);
@@ -318,105 +270,93 @@ static int pack_head_v1(const r2l_ctx* c, std::vector<char>& out, int f16 = 0);
 
 static bool default_acts(const r2l_ctx* c) { return c->act_head == 0.0f && c->act_in == 0.0f && c->act_out == 1.0f && c->block_resid == 1; }
 
+// The steps of build_image for a split mode, in the order it takes them.
+// body + tail: the v3 stream of the mode (`body` stays for the calibration operands, which read its aux blocks)
+static int build_body_stream(r2l_ctx* c, int mode, std::vector<char>& body) {
+    int rc = pack_body_v3(c, stream_of(mode), body, &c->aux_off, &c->tail_off);
+    if (rc) return rc;
+    c->body_mode = mode;
+    return c->d_body.upload(body.data(), body.size(), "body stream");
+}
+
+// the split rungs: the three-pass stream for the blocks in front of the split; behind it room for the aux blocks of a truncated
+// bf6 launch (r2l_launch_split_aux, per slice).  Every other mode holds none
+static int build_three_pass_stream(r2l_ctx* c, int mode) {
+    c->d_body2.release();
+    if (!two_part(mode) || c->n_block < 1) return R2L_OK;
+    std::vector<char> body2;
+    int rc = pack_body_v3(c, R2L_STREAM_F16, body2, &c->aux_off2, &c->tail_off2);
+    if (rc) return rc;
+    c->aux_split_off = body2.size();
+    return c->d_body2.upload(body2.data(), body2.size(), "three-pass body stream", (size_t)c->n_block * R2L_BODY_AUX_BYTES);
+}
+
+// calibration operands: per block W1^T | b1' (the folded bias, real units) | W2^T in fp32
+static int build_calib_operands(r2l_ctx* c, const std::vector<char>& body) {
+    if (c->n_block < 1) return R2L_OK;
+    const size_t per = 2 * 65536 + 256;
+    std::vector<float> wc((size_t)c->n_block * per);
+    for (int b = 0; b < c->n_block; ++b) {
+        const float* W1 = c->host_w[2 + 4 * b].data();
+        const float* W2 = c->host_w[4 + 4 * b].data();
+        const float* auxb = reinterpret_cast<const float*>(body.data() + c->aux_off + (size_t)b * R2L_BODY_AUX_BYTES);
+        float* o = wc.data() + (size_t)b * per;
+        for (int k = 0; k < 256; ++k)
+            for (int f = 0; f < 256; ++f) {
+                o[k * 256 + f] = W1[(size_t)f * 256 + k];
+                o[65536 + 256 + k * 256 + f] = W2[(size_t)f * 256 + k];
+            }
+        for (int f = 0; f < 256; ++f) o[65536 + f] = auxb[f] / c->act_scale;
+    }
+    int rc = c->d_wcal.upload(wc.data(), wc.size(), "calibration operands");
+    // the maxima of an open measurement (calib_started) live in d_stats: a mode change in between re-packs the streams but must
+    // keep them.  2 n_block + 1 words, n_block is fixed for the life of the context: the first call allocates, no later one does
+    return rc ? rc : c->d_stats.grow((size_t)2 * c->n_block + 1, "calibration maxima");
+}
+
+// range tracking words (allocated once, cleared by every re-pack) and the exponents pack_body_v3 has just put into the aux blocks
+static int reset_range_words(r2l_ctx* c) {
+    const size_t nset1 = (size_t)2 * c->n_block + 1;
+    int rc = c->d_range.grow(4 + 2 * nset1, "range tracking words");
+    if (rc) return rc;
+    c->d_gstats = c->d_range + 4;
+    c->d_exps = reinterpret_cast<int*>(c->d_gstats + nset1);
+    std::vector<int> ex(nset1);
+    for (size_t j = 0; j < nset1; ++j) ex[j] = j < c->act.size() ? c->act[j] : R2L_ACT_EXP;
+    if (c->n_block > 0) ex[nset1 - 1] = ex[0];
+    HIPCHK(hipMemset(c->d_range, 0, (4 + nset1) * sizeof(unsigned)), "range tracking words");
+    HIPCHK(hipMemcpy(c->d_exps, ex.data(), nset1 * sizeof(int), hipMemcpyHostToDevice), "range tracking words");
+    return R2L_OK;
+}
+
+// the h0 buffer of the context's own frame: nothing is allocated inside a render of <= H x W rays
+static int ensure_frame_x(r2l_ctx* c) {
+    const long long frame_tiles = ((long long)c->H * c->W + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
+    return ensure_x(c, (int)(frame_tiles < R2L_SLICE_TILES ? frame_tiles : R2L_SLICE_TILES), false);
+}
+
 static int build_image(r2l_ctx* c, int mode) {
-    std::vector<char> img;
+    std::vector<char> img, body;
     if (split_mode(mode) && !default_acts(c))
         return r2l_set_error(R2L_EINVAL, "activation slopes head %g / inner %g / out %g: the generated kernels (fp16_fp8, fp16_e4m3, "
                                          "fp16x3_asm) are built for relu / relu / none (act=relu, trial.inact=relu, trial.outact=none); "
                                          "fp16x3 renders the others", c->act_head, c->act_in, c->act_out);
     if (split_mode(mode)) {
-        // head launch: the stream of r2l_head_kernel (bf6 terms in both modes); body + tail: the v3 stream of the mode
+        // head launch: the stream of r2l_head_kernel (bf6 terms in both modes), packed first -- weights it refuses change nothing --
+        // and uploaded last
         int rc = pack_head_v1(c, img, head_x3(mode));
+        if (rc == R2L_OK) rc = build_body_stream(c, mode, body);
+        if (rc == R2L_OK) rc = build_three_pass_stream(c, mode);
+        if (rc == R2L_OK) rc = build_calib_operands(c, body);
+        if (rc == R2L_OK) rc = reset_range_words(c);
         if (rc) return rc;
-        std::vector<char> body;
-        rc = pack_body_v3(c, stream_of(mode), body, &c->aux_off, &c->tail_off);
-        if (rc) return rc;
-        c->body_mode = mode;
-        if (c->d_body) {
-            (void)hipFree(c->d_body);
-            c->d_body = nullptr;
-        }
-        hipError_t eb = hipMalloc((void**)&c->d_body, body.size());
-        if (eb != hipSuccess) return r2l_set_error(R2L_EHIP, "hipMalloc body stream: %s", hipGetErrorString(eb));
-        eb = hipMemcpy(c->d_body, body.data(), body.size(), hipMemcpyHostToDevice);
-        if (eb != hipSuccess) return r2l_set_error(R2L_EHIP, "hipMemcpy body stream: %s", hipGetErrorString(eb));
-        c->body_bytes = body.size();
-        if (c->d_body2) {
-            (void)hipFree(c->d_body2);
-            c->d_body2 = nullptr;
-        }
-        if (two_part(mode) && c->n_block > 0) {     // ... and the three-pass stream for the blocks in front of the split
-            std::vector<char> body2;
-            rc = pack_body_v3(c, R2L_STREAM_F16, body2, &c->aux_off2, &c->tail_off2);
-            if (rc) return rc;
-            // behind it: room for the aux blocks of a truncated bf6 launch (r2l_launch_split_aux, per slice)
-            c->aux_split_off = body2.size();
-            eb = hipMalloc((void**)&c->d_body2, body2.size() + (size_t)c->n_block * R2L_BODY_AUX_BYTES);
-            if (eb == hipSuccess) eb = hipMemcpy(c->d_body2, body2.data(), body2.size(), hipMemcpyHostToDevice);
-            if (eb != hipSuccess) return r2l_set_error(R2L_EHIP, "three-pass body stream: %s", hipGetErrorString(eb));
-            c->body2_bytes = body2.size();
-        }
-        // calibration operands: per block W1^T | b1' (the folded bias, real units) | W2^T in fp32
-        if (c->n_block > 0) {
-            const size_t per = 2 * 65536 + 256;
-            std::vector<float> wc((size_t)c->n_block * per);
-            for (int b = 0; b < c->n_block; ++b) {
-                const float* W1 = c->host_w[2 + 4 * b].data();
-                const float* W2 = c->host_w[4 + 4 * b].data();
-                const float* auxb = reinterpret_cast<const float*>(body.data() + c->aux_off + (size_t)b * R2L_BODY_AUX_BYTES);
-                float* o = wc.data() + (size_t)b * per;
-                for (int k = 0; k < 256; ++k)
-                    for (int f = 0; f < 256; ++f) {
-                        o[k * 256 + f] = W1[(size_t)f * 256 + k];
-                        o[65536 + 256 + k * 256 + f] = W2[(size_t)f * 256 + k];
-                    }
-                for (int f = 0; f < 256; ++f) o[65536 + f] = auxb[f] / c->act_scale;
-            }
-            if (c->d_wcal) (void)hipFree(c->d_wcal);
-            c->d_wcal = nullptr;
-            eb = hipMalloc((void**)&c->d_wcal, wc.size() * sizeof(float));
-            if (eb == hipSuccess) eb = hipMemcpy(c->d_wcal, wc.data(), wc.size() * sizeof(float), hipMemcpyHostToDevice);
-            // the maxima of an open measurement (calib_started) live in d_stats: a mode change in between re-packs the streams but must
-            // keep them.  2 n_block + 1 words, n_block is fixed for the life of the context: allocated once
-            if (eb == hipSuccess && !c->d_stats) eb = hipMalloc((void**)&c->d_stats, (size_t)(2 * c->n_block + 1) * sizeof(unsigned));
-            if (eb != hipSuccess) return r2l_set_error(R2L_EHIP, "calibration operands: %s", hipGetErrorString(eb));
-        }
-        // range tracking words; the h0 buffer of the context's own frame: nothing is allocated inside a render of <= H x W rays
-        const size_t nset1 = (size_t)2 * c->n_block + 1;
-        if (!c->d_range) {
-            eb = hipMalloc((void**)&c->d_range, (4 + 2 * nset1) * sizeof(unsigned));
-            if (eb == hipSuccess) {
-                c->d_gstats = c->d_range + 4;
-                c->d_exps = reinterpret_cast<int*>(c->d_gstats + nset1);
-            }
-        }
-        if (eb == hipSuccess) eb = hipMemset(c->d_range, 0, (4 + nset1) * sizeof(unsigned));
-        if (eb == hipSuccess) {      // the exponents pack_body_v3 has just put into the aux blocks
-            std::vector<int> ex(nset1);
-            for (size_t j = 0; j < nset1; ++j) ex[j] = j < c->act.size() ? c->act[j] : R2L_ACT_EXP;
-            if (c->n_block > 0) ex[nset1 - 1] = ex[0];
-            eb = hipMemcpy(c->d_exps, ex.data(), nset1 * sizeof(int), hipMemcpyHostToDevice);
-        }
-        if (eb != hipSuccess) return r2l_set_error(R2L_EHIP, "range tracking words: %s", hipGetErrorString(eb));
         c->n_body = c->n_guarded = c->n_since_load = 0;
-        {
-            const long long frame_tiles = ((long long)c->H * c->W + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
-            int rc = ensure_x(c, (int)(frame_tiles < R2L_SLICE_TILES ? frame_tiles : R2L_SLICE_TILES), false);
-            if (rc) return rc;
-        }
+        rc = ensure_frame_x(c);
+        if (rc) return rc;
     } else {
         pack_image_host(c, mode, img);
     }
-    if (c->d_img[mode]) {
-        (void)hipFree(c->d_img[mode]);
-        c->d_img[mode] = nullptr;
-    }
-    hipError_t e = hipMalloc((void**)&c->d_img[mode], img.size());
-    if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "hipMalloc image: %s", hipGetErrorString(e));
-    e = hipMemcpy(c->d_img[mode], img.data(), img.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "hipMemcpy image: %s", hipGetErrorString(e));
-    c->img_bytes[mode] = img.size();
-    return R2L_OK;
+    return c->d_img[mode].upload(img.data(), img.size(), "image");
 }
 
 // host-only: the packed chunk stream of r2l_common.h (no GPU needed; also behind r2l_debug_pack_host)
@@ -733,11 +673,7 @@ int r2l_load_weights(r2l_ctx* c, const float* const* tensors, int n_tensors) {
         if (!tensors[i]) return r2l_set_error(R2L_EINVAL, "tensor %d is NULL", i);
         c->host_w.emplace_back(tensors[i], tensors[i] + n);
     }
-    for (int m = 0; m < R2L_N_MODES; ++m)
-        if (c->d_img[m]) {
-            (void)hipFree(c->d_img[m]);
-            c->d_img[m] = nullptr;
-        }
+    for (auto& img : c->d_img) img.release();
     c->act.assign((size_t)2 * c->n_block + 1, R2L_ACT_EXP);
     c->calib_pending = 1;   // the first FP16_FP8 render measures the activation ranges of these weights
     c->calib_started = 0;
@@ -1046,21 +982,6 @@ static void fill_common(const r2l_ctx* c, R2LParams& p) {
     p.scratch = c->d_scratch;
 }
 
-static int timing_events(r2l_ctx* c, hipEvent_t* e0, hipEvent_t* e1) {
-    if (c->ev_used + 2 > (int)c->ev.size()) {
-        for (int i = 0; i < 2; ++i) {
-            hipEvent_t e;
-            hipError_t er = hipEventCreate(&e);
-            if (er != hipSuccess) return r2l_set_error(R2L_EHIP, "hipEventCreate: %s", hipGetErrorString(er));
-            c->ev.push_back(e);
-        }
-    }
-    *e0 = c->ev[c->ev_used];
-    *e1 = c->ev[c->ev_used + 1];
-    c->ev_used += 2;
-    return R2L_OK;
-}
-
 // FP16_FP8: head launch -> hand-scheduled body launch (which ends every ray tile with the tail layer when the network has
 // the global skip; else -> tail launch) per slice of <= R2L_SLICE_TILES ray tiles; the slices reuse the library-owned h0
 // buffer (1 KiB per ray), stream-ordered.  The timing events bracket the body launch (the dominant kernel).
@@ -1068,19 +989,9 @@ static int ensure_x(r2l_ctx* c, int tiles, bool need_xb) {
     // d_xa is sized for the context's frame at r2l_load_weights; only a call with more rays than H x W (r2l_render_rays,
     // several poses) grows it -- hipFree synchronises the device, so such a call is not stream-ordered the first time.
     // d_xb exists only for the unfused form (networks without the global skip; r2l_debug_set_fused_tail(0)).
-    auto grow = [&](float** buf, int* cap) -> int {
-        if (tiles <= *cap) return R2L_OK;
-        if (*buf) (void)hipFree(*buf);
-        *buf = nullptr;
-        *cap = 0;
-        const size_t bytes = (size_t)tiles * R2L_TILE_RAYS * R2L_WIDTH * sizeof(float);
-        hipError_t e = hipMalloc((void**)buf, bytes);
-        if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "hipMalloc x buffer (%zu B): %s", bytes, hipGetErrorString(e));
-        *cap = tiles;
-        return R2L_OK;
-    };
-    int rc = grow(&c->d_xa, &c->x_tiles);
-    if (rc == R2L_OK && need_xb) rc = grow(&c->d_xb, &c->xb_tiles);
+    const size_t numel = (size_t)tiles * R2L_TILE_RAYS * R2L_WIDTH;
+    int rc = c->d_xa.grow(numel, "x buffer");
+    if (rc == R2L_OK && need_xb) rc = c->d_xb.grow(numel, "x buffer");
     return rc;
 }
 
@@ -1182,15 +1093,11 @@ static int launch_split(r2l_ctx* c, const R2LParams& p, hipStream_t s) {
             ++c->n_since_load;
             ++c->n_body;
             c->n_guarded += guard ? 1 : 0;
-            hipEvent_t e0 = nullptr, e1 = nullptr;
-            if (c->timing) {
-                rc = timing_events(c, &e0, &e1);
-                if (rc) return rc;
-                (void)hipEventRecord(e0, s);
-            }
+            rc = c->timer.start(s);
+            if (rc) return rc;
             e = r2l_launch_body(pb, grid, s);
             if (e == hipSuccess && two_bodies) e = r2l_launch_body(p2, grid, s);
-            if (c->timing) (void)hipEventRecord(e1, s);
+            c->timer.stop(s);
             if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "r2l body launch: %s", hipGetErrorString(e));
             body_out = c->d_xb;
         }
@@ -1238,14 +1145,10 @@ static int timed_launch(r2l_ctx* c, const R2LParams& p, hipStream_t s) {
 static int render_launch(r2l_ctx* c, const R2LParams& p, hipStream_t s) {
     if (split_mode(c->mode)) return launch_split(c, p, s);
     const int grid = balanced_grid(p.n_tiles, c->n_cu);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (c->timing) {
-        int rc = timing_events(c, &e0, &e1);
-        if (rc) return rc;
-        (void)hipEventRecord(e0, s);
-    }
+    int rc = c->timer.start(s);
+    if (rc) return rc;
     hipError_t e = r2l_launch_resmlp(p, c->mode, grid, s);
-    if (c->timing) (void)hipEventRecord(e1, s);
+    c->timer.stop(s);
     if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "r2l_resmlp launch: %s", hipGetErrorString(e));
     return R2L_OK;
 }
@@ -1331,30 +1234,18 @@ long long r2l_kernel_flops_per_ray(const r2l_ctx* c) {
 }
 long long r2l_weight_image_bytes(const r2l_ctx* c) {
     if (!c) return 0;
-    return (long long)c->img_bytes[c->mode] + (split_mode(c->mode) ? (long long)c->body_bytes : 0) +
-           (two_part(c->mode) ? (long long)c->body2_bytes : 0);
+    return (long long)c->d_img[c->mode].size() + (split_mode(c->mode) ? (long long)c->d_body.size() : 0) +
+           (two_part(c->mode) ? (long long)c->aux_split_off : 0);
 }
 int r2l_rays_per_tile(const r2l_ctx*) { return R2L_TILE_RAYS; }
 
 int r2l_timing_enable(r2l_ctx* c, int on) {
     if (!c) return r2l_set_error(R2L_EINVAL, "NULL ctx");
-    c->timing = on != 0;
+    c->timer.on = on != 0;
     return R2L_OK;
 }
 
 int r2l_kernel_time_ms(r2l_ctx* c, double* total_ms, int* n_launches, int reset) {
     if (!c) return r2l_set_error(R2L_EINVAL, "NULL ctx");
-    double tot = 0;
-    for (int i = 0; i + 1 < c->ev_used; i += 2) {
-        hipError_t e = hipEventSynchronize(c->ev[i + 1]);
-        if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "hipEventSynchronize: %s", hipGetErrorString(e));
-        float ms = 0;
-        e = hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]);
-        if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "hipEventElapsedTime: %s", hipGetErrorString(e));
-        tot += ms;
-    }
-    if (total_ms) *total_ms = tot;
-    if (n_launches) *n_launches = c->ev_used / 2;
-    if (reset) c->ev_used = 0;
-    return R2L_OK;
+    return c->timer.total(total_ms, n_launches, reset);
 }

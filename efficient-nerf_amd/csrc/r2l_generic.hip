@@ -24,9 +24,9 @@
 #include "r2l_device.h"      // to_rev / trig_pow2: sin / cos of the exactly scaled argument
 
 struct r2l_linear {
-    int in_dim, out_dim;
-    float* w_dev;     // [out_dim][in_dim], the state_dict's layout
-    float* b_dev;     // [out_dim] (zeros when the layer has no bias)
+    int in_dim = 0, out_dim = 0;
+    DevBuf<float> w_dev;     // [out_dim][in_dim], the state_dict's layout
+    DevBuf<float> b_dev;     // [out_dim] (zeros when the layer has no bias)
 };
 
 #define GT_M 128      // rays per workgroup (4 waves x 32)
@@ -171,31 +171,23 @@ int r2l_linear_create(r2l_linear** out, const float* w_host, const float* b_host
         return r2l_set_error(R2L_EINVAL, "bad argument to r2l_linear_create (out_dim=%d in_dim=%d)", out_dim, in_dim);
     int rc = r2l_require_gfx950(nullptr);
     if (rc) return rc;
-    r2l_linear* l = new r2l_linear{in_dim, out_dim, nullptr, nullptr};
-    const size_t wn = (size_t)out_dim * in_dim;
-    hipError_t e = hipMalloc(&l->w_dev, wn * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&l->b_dev, (size_t)out_dim * sizeof(float));
-    if (e == hipSuccess) e = hipMemcpy(l->w_dev, w_host, wn * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        std::vector<float> zero;
-        if (!b_host) zero.assign(out_dim, 0.0f);
-        e = hipMemcpy(l->b_dev, b_host ? b_host : zero.data(), (size_t)out_dim * sizeof(float), hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) {
-        if (l->w_dev) (void)hipFree(l->w_dev);
-        if (l->b_dev) (void)hipFree(l->b_dev);
+    r2l_linear* l = new r2l_linear();
+    l->in_dim = in_dim;
+    l->out_dim = out_dim;
+    std::vector<float> zero;
+    if (!b_host) zero.assign(out_dim, 0.0f);
+    rc = l->w_dev.upload(w_host, (size_t)out_dim * in_dim, "r2l_linear_create");
+    if (rc == R2L_OK) rc = l->b_dev.upload(b_host ? b_host : zero.data(), (size_t)out_dim, "r2l_linear_create");
+    if (rc) {
         delete l;
-        return r2l_set_error(R2L_EHIP, "r2l_linear_create: %s", hipGetErrorString(e));
+        return rc;
     }
     *out = l;
     return R2L_OK;
 }
 
 void r2l_linear_destroy(r2l_linear* l) {
-    if (!l) return;
-    (void)hipFree(l->w_dev);
-    (void)hipFree(l->b_dev);
-    delete l;
+    if (l) delete l;
 }
 
 int r2l_linear_forward(const r2l_linear* l, const float* x_dev, long long ldx, int n, float* y_dev, long long ldy,
@@ -213,7 +205,7 @@ int r2l_linear_forward(const r2l_linear* l, const float* x_dev, long long ldx, i
         return r2l_set_error(R2L_EINVAL, "r2l_linear_forward: x and y overlap");
     if (n == 0) return R2L_OK;
     dim3 grid((unsigned)((n + GT_M - 1) / GT_M), (unsigned)((l->out_dim + GT_N - 1) / GT_N));
-    hipLaunchKernelGGL(r2l_linear_kernel, grid, dim3(256), 0, (hipStream_t)stream, x_dev, ldx, n, l->in_dim, l->w_dev, l->b_dev,
+    hipLaunchKernelGGL(r2l_linear_kernel, grid, dim3(256), 0, (hipStream_t)stream, x_dev, ldx, n, l->in_dim, l->w_dev.get(), l->b_dev.get(),
                        l->out_dim, y_dev, ldy, res_dev, ldr, res_scale, act, post_dev, ldp);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return r2l_set_error(R2L_EHIP, "r2l_linear_forward launch: %s", hipGetErrorString(e));

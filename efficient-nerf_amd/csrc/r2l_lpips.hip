@@ -38,10 +38,10 @@
 #define LPIPS_GROUP_PIXELS 4096          // ... as many as bring conv 3 .. 5 to this many pixels per side of the pairs (64 row tiles)
 
 struct r2l_lpips_ctx {
-    float* dev;                          // one allocation: weights, biases, lin vectors
-    const float* w[LPIPS_LAYERS];        // [out][kh kw in]: the state_dict's [out][in][kh][kw] reordered
-    const float* b[LPIPS_LAYERS];
-    const float* lin[LPIPS_LAYERS];
+    DevBuf<float> dev;                   // one allocation: weights, biases, lin vectors; the rest are views into it
+    const float* w[LPIPS_LAYERS] = {};   // [out][kh kw in]: the state_dict's [out][in][kh][kw] reordered
+    const float* b[LPIPS_LAYERS] = {};
+    const float* lin[LPIPS_LAYERS] = {};
 };
 
 namespace {
@@ -247,12 +247,10 @@ int r2l_lpips_create(r2l_lpips_ctx** out, const float* const* tensors_host, int 
                 for (int t = 0; t < kk; ++t) host[off[i] + ((size_t)o * kk + t) * C + c] = tensors_host[i][((size_t)o * C + c) * kk + t];
     }
     r2l_lpips_ctx* l = new r2l_lpips_ctx();
-    hipError_t err = hipMalloc(&l->dev, host.size() * sizeof(float));
-    if (err == hipSuccess) err = hipMemcpy(l->dev, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (err != hipSuccess) {
-        if (l->dev) (void)hipFree(l->dev);
+    e = l->dev.upload(host.data(), host.size(), "r2l_lpips_create");
+    if (e) {
         delete l;
-        return r2l_set_error(R2L_EHIP, "r2l_lpips_create: %s", hipGetErrorString(err));
+        return e;
     }
     for (int k = 0; k < LPIPS_LAYERS; ++k) {
         l->w[k] = l->dev + off[k];
@@ -264,9 +262,7 @@ int r2l_lpips_create(r2l_lpips_ctx** out, const float* const* tensors_host, int 
 }
 
 void r2l_lpips_destroy(r2l_lpips_ctx* l) {
-    if (!l) return;
-    (void)hipFree(l->dev);
-    delete l;
+    if (l) delete l;
 }
 
 long long r2l_lpips_workspace_floats(int H, int W) {
