@@ -26,6 +26,7 @@
 
 #include "../../include/r2l_hip.h"
 #include "nerf_kernels.h"
+#include "nerf_scan.h"
 #include "r2l_device.h"
 #include "r2l_ray_math.h"
 
@@ -633,52 +634,10 @@ __global__ void nerf_ndc_rays_kernel(const float* __restrict__ rays_o, const flo
 }
 
 // ====================================================================================
-// wave-level scans (64 lanes)
+// The scan: one wave per ray, four rays per block.  Every kernel is the ray's pointer set-up plus calls of nerf_scan.h, where
+// the arithmetic and the reference's line numbers live.
 // ====================================================================================
-__device__ __forceinline__ double shfl_up_f64(double v, int delta) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl_up(lo, delta, 64);
-    hi = __shfl_up(hi, delta, 64);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double shfl_xor_f64(double v, int mask) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl_xor(lo, mask, 64);
-    hi = __shfl_xor(hi, mask, 64);
-    return __hiloint2double(hi, lo);
-}
-// inclusive product / sum scans across the wave in double precision (torch's CPU cumprod /
-// cumsum accumulate float tensors in double and round each output to float)
-__device__ __forceinline__ double wave_scan_mul(double v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        double u = shfl_up_f64(v, d);
-        if (lane >= d) v *= u;
-    }
-    return v;
-}
-__device__ __forceinline__ double wave_scan_add(double v, int lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        double u = shfl_up_f64(v, d);
-        if (lane >= d) v += u;
-    }
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
-}
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += shfl_xor_f64(v, m);
-    return v;
-}
-
-// ====================================================================================
-// raw2outputs: one wave per ray, C consecutive samples per lane
-// ====================================================================================
+// raw2outputs: C consecutive samples per lane
 template <int C>
 __global__ __launch_bounds__(256) void nerf_raw2outputs_kernel(const float* __restrict__ raw,
                                                                const float* __restrict__ z, int z_stride,
@@ -692,116 +651,14 @@ __global__ __launch_bounds__(256) void nerf_raw2outputs_kernel(const float* __re
     const int ray = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (ray >= n) return;
-    const float* zr = z + (size_t)ray * z_stride;
-    const float dx = rays_d[(size_t)ray * 3 + 0], dy = rays_d[(size_t)ray * 3 + 1], dz = rays_d[(size_t)ray * 3 + 2];
-    const float norm = sqrtf(__fadd_rn(__fadd_rn(dx * dx, dy * dy), dz * dz));  // torch.norm(rays_d, dim=-1)
-    float alpha[C], zi[C], cr[C], cg[C], cb[C];
-    double lp[C];
-    double prod = 1.0;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const int i = lane * C + c;
-        const bool ok = i < S;
-        const int ii = ok ? i : S - 1;
-        const float zc = zr[ii];
-        const float zn = zr[ii + 1 < S ? ii + 1 : S - 1];
-        float dist = (ii < S - 1) ? (zn - zc) : 1e10f;  // dists = cat(z[1:]-z[:-1], 1e10)
-        dist = dist * norm;
-        const f32x4 r4 = *reinterpret_cast<const f32x4*>(raw + ((size_t)ray * S + ii) * 4);
-        // raw2alpha(raw[..., 3] + noise, dists), noise = randn * raw_noise_std drawn by the caller (main.py:592-600)
-        const float pre = noise ? r4[3] + noise[(size_t)ray * S + ii] : r4[3];
-        const float sig = (pre != pre) ? pre : fmaxf(pre, 0.0f);  // F.relu: a NaN stays a NaN (fmaxf alone returns the 0)
-        float a = 1.0f - expf(-sig * dist);                   // 1 - exp(-relu(raw) * dists)
-        if (!ok) a = 0.0f;
-        alpha[c] = a;
-        zi[c] = zc;
-        cr[c] = 1.0f / (1.0f + expf(-r4[0]));                 // torch.sigmoid
-        cg[c] = 1.0f / (1.0f + expf(-r4[1]));
-        cb[c] = 1.0f / (1.0f + expf(-r4[2]));
-        lp[c] = prod;                                          // exclusive product inside the lane
-        const float pterm = ok ? ((1.0f - a) + 1e-10f) : 1.0f; // 1 - alpha + 1e-10, float ops
-        prod *= (double)pterm;
-    }
-    const double incl = wave_scan_mul(prod, lane);
-    double excl = shfl_up_f64(incl, 1);
-    if (lane == 0) excl = 1.0;
-    float sr = 0.f, sg = 0.f, sb = 0.f, sd = 0.f, sa = 0.f;
-#pragma unroll
-    for (int c = 0; c < C; ++c) {
-        const int i = lane * C + c;
-        const float T = (float)(excl * lp[c]);  // cumprod accumulated in double, rounded per element
-        const float w = alpha[c] * T;
-        if (i < S) {
-            if (weights_out) weights_out[(size_t)ray * S + i] = w;
-            sr += w * cr[c];
-            sg += w * cg[c];
-            sb += w * cb[c];
-            sd += w * zi[c];
-            sa += w;
-        }
-    }
-    sr = wave_sum(sr);
-    sg = wave_sum(sg);
-    sb = wave_sum(sb);
-    sd = wave_sum(sd);
-    sa = wave_sum(sa);
-    if (lane == 0) {
-        if (white_bkgd) {
-            const float bg = 1.0f - sa;
-            sr += bg;
-            sg += bg;
-            sb += bg;
-        }
-        if (rgb_map) {
-            rgb_map[(size_t)ray * 3 + 0] = sr;
-            rgb_map[(size_t)ray * 3 + 1] = sg;
-            rgb_map[(size_t)ray * 3 + 2] = sb;
-        }
-        if (depth_map) depth_map[ray] = sd;
-        if (acc_map) acc_map[ray] = sa;
-        if (disp_map) {
-            const float q = sd / sa;
-            // torch.max(1e-10, q) propagates NaN (0/0 for empty rays), fmaxf would not
-            const float m = (q != q) ? q : fmaxf(1e-10f, q);
-            disp_map[ray] = 1.0f / m;
-        }
-    }
+    scan_composite<C>(raw + (size_t)ray * S * 4, z + (size_t)ray * z_stride, noise ? noise + (size_t)ray * S : nullptr, S,
+                      ray_norm(rays_d, ray), white_bkgd, lane, ray, weights_out ? weights_out + (size_t)ray * S : nullptr, nullptr,
+                      rgb_map, disp_map, acc_map, depth_map);
 }
 
-// ====================================================================================
-// sample_pdf: one wave per ray, n_bins <= 64  (utils/run_nerf_raybased_helpers.py:283-330; the reference runs it
-// on the CPU, main.py:723-728, so the float accumulation orders below are ATen's CPU orders)
-// ====================================================================================
-// torch.sum(x, -1) of a contiguous float row on the CPU (ATen SumKernel, vectorized_inner_sum): 8-lane vectors,
-// 4 interleaved vector accumulators over groups of 4 vectors, the remaining whole vectors into accumulator 0,
-// ((a0 + a1) + a2) + a3 per lane, then a scalar chain: the row's tail elements first, then the 8 lane sums.
-// Verified bit for bit against torch.sum on rows of 30 .. 190 floats (tools/torch_sum_order.py).
-__device__ __forceinline__ float torch_cpu_row_sum(const float* row /* LDS, zero padded to 64 */, float* cols /* LDS [8] */,
-                                                   int nw, int lane) {
-    const int nv = nw >> 3, full = (nv >> 2) << 2;
-    if (lane < 8) {
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        for (int v = 0; v < full; v += 4) {
-            a0 = __fadd_rn(a0, row[(v + 0) * 8 + lane]);
-            a1 = __fadd_rn(a1, row[(v + 1) * 8 + lane]);
-            a2 = __fadd_rn(a2, row[(v + 2) * 8 + lane]);
-            a3 = __fadd_rn(a3, row[(v + 3) * 8 + lane]);
-        }
-        for (int v = full; v < nv; ++v) a0 = __fadd_rn(a0, row[v * 8 + lane]);
-        cols[lane] = __fadd_rn(__fadd_rn(__fadd_rn(a0, a1), a2), a3);
-    }
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    float fin = 0.f;
-    for (int k = nv * 8; k < nw; ++k) fin = __fadd_rn(fin, row[k]);
-    for (int k = 0; k < 8; ++k) fin = __fadd_rn(fin, cols[k]);
-    return fin;
-}
-
-// bins: [n, n_bins] (stride 0 = one shared row); with bins_are_z the row holds n_bins + 1 depths and
-// bins = .5 * (z[1:] + z[:-1]) (main.py:722).  u: nullptr = torch.linspace(0, 1, N) (det, evaluated here by the
-// scalar formula), else [N] (u_stride 0) or one row per ray (u_stride = N: the perturb > 0 path draws u per ray).
-// cdf_out [n, n_bins], inds_out [n, N] (searchsorted(cdf, u, right=True)): optional parity taps.
+// sample_pdf, n_bins <= 64.  bins: [n, n_bins] (stride 0 = one shared row); with bins_are_z the row holds n_bins + 1 depths.
+// u: nullptr = torch.linspace(0, 1, N) (det), else [N] (u_stride 0) or one row per ray (u_stride = N: the perturb > 0 path draws
+// u per ray).  cdf_out [n, n_bins], inds_out [n, N] (searchsorted(cdf, u, right=True)): optional parity taps.
 __global__ __launch_bounds__(256) void nerf_sample_pdf_kernel(const float* __restrict__ bins, int bins_stride, int bins_are_z,
                                                               const float* __restrict__ weights, int w_stride,
                                                               int w_off, int n, int n_bins,
@@ -816,50 +673,16 @@ __global__ __launch_bounds__(256) void nerf_sample_pdf_kernel(const float* __res
     const int ray = blockIdx.x * 4 + wv;
     const int lane = threadIdx.x & 63;
     if (ray >= n) return;
-    const int nw = n_bins - 1;
-    float w = 0.0f;
-    if (lane < nw) w = weights[(size_t)ray * w_stride + w_off + lane] + 1e-5f;  // weights + 1e-5
-    s_w[wv][lane] = w;
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    const float total = torch_cpu_row_sum(s_w[wv], s_col[wv], nw, lane);          // torch.sum(weights, -1)
-    const float pdf = (lane < nw) ? w / total : 0.0f;
-    const double cs = wave_scan_add((double)pdf, lane);                          // cumsum (double accumulate)
-    if (lane < nw) s_cdf[wv][lane + 1] = (float)cs;
-    if (lane == 63) s_cdf[wv][0] = 0.0f;                                          // cat(zeros, cdf)
-    if (lane < n_bins) {
-        const float* br = bins + (size_t)ray * bins_stride;
-        s_bins[wv][lane] = bins_are_z ? 0.5f * __fadd_rn(br[lane + 1], br[lane]) : br[lane];
-    }
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    pdf_tables(weights + (size_t)ray * w_stride + w_off, bins + (size_t)ray * bins_stride, bins_are_z, n_bins, s_w[wv], s_col[wv],
+               s_cdf[wv], s_bins[wv], lane);
     if (cdf_out && lane < n_bins) cdf_out[(size_t)ray * n_bins + lane] = s_cdf[wv][lane];
-    const float step = N > 1 ? 1.0f / (float)(N - 1) : 0.0f;
     for (int k = lane; k < N; k += 64) {
-        float u;
-        if (u_arr) u = u_arr[(size_t)ray * u_stride + k];
-        else u = (k < N / 2 || N == 1) ? __fmul_rn(step, (float)k) : __fsub_rn(1.0f, __fmul_rn(step, (float)(N - k - 1)));
-        int lo = 0, hi = n_bins;  // searchsorted(cdf, u, right=True) as ATen writes it, !(cdf[mid] > u): a NaN on either side goes right
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (!(s_cdf[wv][mid] > u)) lo = mid + 1; else hi = mid;
-        }
+        int lo;
+        samples[(size_t)ray * N + k] =
+            pdf_draw(s_cdf[wv], s_bins[wv], n_bins, u_arr ? u_arr[(size_t)ray * u_stride + k] : linspace_u(k, N), lo);
         if (inds_out) inds_out[(size_t)ray * N + k] = lo;
-        const int below = lo - 1 > 0 ? lo - 1 : 0;
-        const int above = lo < n_bins - 1 ? lo : n_bins - 1;
-        const float c0 = s_cdf[wv][below], c1 = s_cdf[wv][above];
-        const float b0 = s_bins[wv][below], b1 = s_bins[wv][above];
-        float denom = c1 - c0;
-        if (denom < 1e-5f) denom = 1.0f;
-        const float t = (u - c0) / denom;
-        samples[(size_t)ray * N + k] = b0 + t * (b1 - b0);
     }
 }
-
-// torch.sort's order of floats: ascending, every NaN behind every number (+inf included), NaNs equal among themselves; -0 == 0.
-// A total preorder, which the bitonic network and the rank searches of the merge need: with a plain < every comparison against
-// a NaN is false, the network no longer sorts the numbers and two ranks of the merge coincide (a slot stays unwritten).
-__device__ __forceinline__ bool nerf_before(float a, float b) { return a < b || (a == a && b != b); }
 
 // rows of N <= 256 floats sorted ascending (bitonic network in LDS, one wave per row): with random uniforms
 // (perturb > 0) sample_pdf's output is not monotone and the reference's sort (main.py:730-732) is a real sort
@@ -872,8 +695,7 @@ __global__ __launch_bounds__(256) void nerf_sort_rows_kernel(const float* __rest
     for (int i = lane; i < 256; i += 64) s[wv][i] = i < N ? x[(size_t)ray * N + i] : __builtin_nanf("");  // the padding sorts last
     for (int k = 2; k <= 256; k <<= 1)
         for (int j = k >> 1; j > 0; j >>= 1) {
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+            wave_sync();
             for (int i = lane; i < 256; i += 64) {
                 const int p = i ^ j;
                 if (p > i) {
@@ -886,8 +708,7 @@ __global__ __launch_bounds__(256) void nerf_sort_rows_kernel(const float* __rest
                 }
             }
         }
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    wave_sync();
     for (int i = lane; i < N; i += 64) out[(size_t)ray * N + i] = s[wv][i];
 }
 
@@ -908,9 +729,7 @@ __global__ __launch_bounds__(256) void nerf_row_std_kernel(const float* __restri
     if (lane == 0) out[ray] = (float)sqrt(var);
 }
 
-// ====================================================================================
-// merge of two ascending rows (the reference sorts the concatenation): one wave per ray
-// ====================================================================================
+// merge of two ascending rows of at most 256
 __global__ __launch_bounds__(256) void nerf_merge_kernel(const float* __restrict__ a, int a_stride, int na,
                                                          const float* __restrict__ b, int nb, int n,
                                                          float* __restrict__ out) {
@@ -922,36 +741,15 @@ __global__ __launch_bounds__(256) void nerf_merge_kernel(const float* __restrict
     if (ray >= n) return;
     for (int i = lane; i < na; i += 64) s_a[wv][i] = a[(size_t)ray * a_stride + i];
     for (int i = lane; i < nb; i += 64) s_b[wv][i] = b[(size_t)ray * nb + i];
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    float* o = out + (size_t)ray * (na + nb);
-    for (int i = lane; i < na; i += 64) {  // rank of a[i] = i + #{b before a[i]}
-        const float v = s_a[wv][i];
-        int lo = 0, hi = nb;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (nerf_before(s_b[wv][mid], v)) lo = mid + 1; else hi = mid;
-        }
-        o[i + lo] = v;
-    }
-    for (int j = lane; j < nb; j += 64) {  // rank of b[j] = j + #{a not behind b[j]}: on a tie a's element first, as a stable sort of cat(a, b)
-        const float v = s_b[wv][j];
-        int lo = 0, hi = na;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (!nerf_before(v, s_a[wv][mid])) lo = mid + 1; else hi = mid;
-        }
-        o[j + lo] = v;
-    }
+    wave_sync();
+    merge_rows(s_a[wv], na, s_b[wv], nb, out + (size_t)ray * (na + nb), lane);
 }
 
-// ====================================================================================
 // coarse pass -> fine depths in ONE launch (main.py:705-732 on the deterministic test path): raw2outputs of the coarse raw,
-// sample_pdf on weights[..., 1:-1] over the midpoints of z, and the merge of z with the samples -- one wave per ray, the weights,
-// the cdf and the samples never leave LDS (stand-alone: three launches, weights and samples through HBM twice).  The arithmetic
-// is the three kernels' above, statement for statement (same float / double orders: the results are bit-identical, asserted by
-// tests/test_teacher_gpu.py); S0 <= 64 coarse samples, N <= 256 fine ones, u one shared row (per-ray uniforms need the sort).
-// ====================================================================================
+// sample_pdf on weights[..., 1:-1] over the midpoints of z, and the merge of z with the samples.  The weights, the cdf and the
+// samples never leave LDS (stand-alone: three launches, weights and samples through HBM twice); the calls are the three kernels'
+// above, so the results are theirs bit for bit (tests/test_teacher_gpu.py runs both).  S0 <= 64 coarse samples, N <= 256 fine
+// ones, u one shared row (per-ray uniforms need the sort).
 __global__ __launch_bounds__(256) void nerf_coarse_scan_kernel(const float* __restrict__ raw, const float* __restrict__ z, int z_stride,
                                                                const float* __restrict__ rays_d, int n, int S, int white_bkgd,
                                                                const float* __restrict__ noise, const float* __restrict__ u_arr, int N,
@@ -969,122 +767,18 @@ __global__ __launch_bounds__(256) void nerf_coarse_scan_kernel(const float* __re
     const int ray = blockIdx.x * 4 + wv;
     const int lane = threadIdx.x & 63;
     if (ray >= n) return;
-    // ---- raw2outputs, C = 1 (nerf_raw2outputs_kernel<1>)
-    const float* zr = z + (size_t)ray * z_stride;
-    const float dx = rays_d[(size_t)ray * 3 + 0], dy = rays_d[(size_t)ray * 3 + 1], dz = rays_d[(size_t)ray * 3 + 2];
-    const float norm = sqrtf(__fadd_rn(__fadd_rn(dx * dx, dy * dy), dz * dz));
-    const bool ok = lane < S;
-    const int ii = ok ? lane : S - 1;
-    const float zc = zr[ii];
-    const float zn = zr[ii + 1 < S ? ii + 1 : S - 1];
-    float dist = (ii < S - 1) ? (zn - zc) : 1e10f;
-    dist = dist * norm;
-    const f32x4 r4 = *reinterpret_cast<const f32x4*>(raw + ((size_t)ray * S + ii) * 4);
-    const float pre = noise ? r4[3] + noise[(size_t)ray * S + ii] : r4[3];
-    const float sig = (pre != pre) ? pre : fmaxf(pre, 0.0f);
-    float a = 1.0f - expf(-sig * dist);
-    if (!ok) a = 0.0f;
-    const float cr = 1.0f / (1.0f + expf(-r4[0])), cg = 1.0f / (1.0f + expf(-r4[1])), cb = 1.0f / (1.0f + expf(-r4[2]));
-    const float pterm = ok ? ((1.0f - a) + 1e-10f) : 1.0f;
-    const double incl = wave_scan_mul((double)pterm, lane);
-    double excl = shfl_up_f64(incl, 1);
-    if (lane == 0) excl = 1.0;
-    const float T = (float)(excl * 1.0);
-    const float wgt = a * T;
-    float sr = 0.f, sg = 0.f, sb = 0.f, sd = 0.f, sa = 0.f;
-    if (ok) {
-        sr = wgt * cr;
-        sg = wgt * cg;
-        sb = wgt * cb;
-        sd = wgt * zc;
-        sa = wgt;
-    }
-    s_wt[wv][lane] = ok ? wgt : 0.0f;
-    s_z[wv][lane] = zc;
-    sr = wave_sum(sr);
-    sg = wave_sum(sg);
-    sb = wave_sum(sb);
-    sd = wave_sum(sd);
-    sa = wave_sum(sa);
-    if (lane == 0) {
-        if (white_bkgd) {
-            const float bg = 1.0f - sa;
-            sr += bg;
-            sg += bg;
-            sb += bg;
-        }
-        if (rgb_map) {
-            rgb_map[(size_t)ray * 3 + 0] = sr;
-            rgb_map[(size_t)ray * 3 + 1] = sg;
-            rgb_map[(size_t)ray * 3 + 2] = sb;
-        }
-        if (acc_map) acc_map[ray] = sa;
-        if (disp_map) {
-            const float q = sd / sa;
-            const float m = (q != q) ? q : fmaxf(1e-10f, q);
-            disp_map[ray] = 1.0f / m;
-        }
-    }
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    // ---- sample_pdf(z_mid, weights[..., 1:-1], N, det) (nerf_sample_pdf_kernel with bins_are_z, w_off = 1)
-    const int n_bins = S - 1, nw = n_bins - 1;
-    float w = 0.0f;
-    if (lane < nw) w = s_wt[wv][1 + lane] + 1e-5f;
-    s_w[wv][lane] = w;
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    const float total = torch_cpu_row_sum(s_w[wv], s_col[wv], nw, lane);
-    const float pdf = (lane < nw) ? w / total : 0.0f;
-    const double cs = wave_scan_add((double)pdf, lane);
-    if (lane < nw) s_cdf[wv][lane + 1] = (float)cs;
-    if (lane == 63) s_cdf[wv][0] = 0.0f;
-    if (lane < n_bins) s_bins[wv][lane] = 0.5f * __fadd_rn(s_z[wv][lane + 1], s_z[wv][lane]);
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    const float step = N > 1 ? 1.0f / (float)(N - 1) : 0.0f;
+    scan_composite<1>(raw + (size_t)ray * S * 4, z + (size_t)ray * z_stride, noise ? noise + (size_t)ray * S : nullptr, S,
+                      ray_norm(rays_d, ray), white_bkgd, lane, ray, s_wt[wv], s_z[wv], rgb_map, disp_map, acc_map, nullptr);
+    wave_sync();
+    pdf_tables(s_wt[wv] + 1, s_z[wv], 1, S - 1, s_w[wv], s_col[wv], s_cdf[wv], s_bins[wv], lane);
     for (int k = lane; k < N; k += 64) {
-        float u;
-        if (u_arr) u = u_arr[k];
-        else u = (k < N / 2 || N == 1) ? __fmul_rn(step, (float)k) : __fsub_rn(1.0f, __fmul_rn(step, (float)(N - k - 1)));
-        int lo = 0, hi = n_bins;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (!(s_cdf[wv][mid] > u)) lo = mid + 1; else hi = mid;
-        }
-        const int below = lo - 1 > 0 ? lo - 1 : 0;
-        const int above = lo < n_bins - 1 ? lo : n_bins - 1;
-        const float c0 = s_cdf[wv][below], c1 = s_cdf[wv][above];
-        const float b0 = s_bins[wv][below], b1 = s_bins[wv][above];
-        float denom = c1 - c0;
-        if (denom < 1e-5f) denom = 1.0f;
-        const float t = (u - c0) / denom;
-        const float smp = b0 + t * (b1 - b0);
+        int lo;
+        const float smp = pdf_draw(s_cdf[wv], s_bins[wv], S - 1, u_arr ? u_arr[k] : linspace_u(k, N), lo);
         s_s[wv][k] = smp;
         samples[(size_t)ray * N + k] = smp;
     }
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    // ---- sort(cat(z, samples)) of two ascending rows (nerf_merge_kernel)
-    float* o = z_all + (size_t)ray * (S + N);
-    if (lane < S) {
-        const float v = s_z[wv][lane];
-        int lo = 0, hi = N;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (nerf_before(s_s[wv][mid], v)) lo = mid + 1; else hi = mid;
-        }
-        o[lane + lo] = v;
-    }
-    for (int j = lane; j < N; j += 64) {
-        const float v = s_s[wv][j];
-        int lo = 0, hi = S;
-        while (lo < hi) {
-            const int mid = (lo + hi) >> 1;
-            if (!nerf_before(v, s_z[wv][mid])) lo = mid + 1; else hi = mid;
-        }
-        o[j + lo] = v;
-    }
+    wave_sync();
+    merge_rows(s_z[wv], S, s_s[wv], N, z_all + (size_t)ray * (S + N), lane);
 }
 
 // ====================================================================================

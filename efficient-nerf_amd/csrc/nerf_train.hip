@@ -3,7 +3,7 @@
 // and, further down, the rays of a step of the use_batching loop straight from the images (nerf_train_batch_rays_kernel).
 // The host mirror composes the step (efficient-nerf_amd/train_teacher.py).
 //
-// Forward (nerf_raw2outputs_kernel): c = sigmoid(raw_rgb), s = relu(raw_sigma + noise), alpha = 1 - exp(-s dist),
+// Forward (scan_composite, nerf_scan.h): c = sigmoid(raw_rgb), s = relu(raw_sigma + noise), alpha = 1 - exp(-s dist),
 // p = 1 - alpha + 1e-10, T_i = prod_{j<i} p_j, w = alpha T, rgb_map = sum_i w_i c_i (+ 1 - sum_i w_i on a white background).
 // The loss reaches rgb_map alone (z_samples is detached, main.py:728), so with g = g_rgb_map and
 //   q_i = g . c_i - (white_bkgd ? g_r + g_g + g_b : 0)                      (= dL/dw_i)
@@ -14,9 +14,9 @@
 // saturated sample.
 //
 // Layout as the forward scan: a wave owns a ray, lane l of chunk k owns sample 64 k + l (a coalesced float4 of raw per lane), any
-// S >= 1.  Pass 1 walks the chunks front to back: T (cumprod accumulated in double and rounded per element, as the forward kernel
-// does) is parked in the density slot of the sample's own g_raw element.  Pass 2 walks them back to front: the forward quantities
-// are recomputed in registers, B is a suffix scan of the affine maps E -> alpha q + p E across the wave (in double) with the carry
+// S >= 1.  Pass 1 walks the chunks front to back: T (cumprod accumulated in double and rounded per element, by the forward's
+// wave_scan_mul) is parked in the density slot of the sample's own g_raw element.  Pass 2 walks them back to front: the forward quantities
+// are recomputed in registers by the forward's own functions (scan_sample, scan_sigmoid, ray_norm), B is a suffix scan of the affine maps E -> alpha q + p E across the wave (in double) with the carry
 // E of the chunk behind, and every g_raw element is written once, whole.  No atomics, no reduction across rays: the same
 // inputs give the same bits.
 #include <hip/hip_runtime.h>
@@ -24,48 +24,9 @@
 #include <stdint.h>
 
 #include "../../include/r2l_hip.h"
+#include "nerf_scan.h"
 #include "r2l_host_util.h"
 #include "r2l_ray_math.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double nt_shfl_up_f64(double v, int delta) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl_up(lo, delta, 64);
-    hi = __shfl_up(hi, delta, 64);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double nt_shfl_down_f64(double v, int delta) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl_down(lo, delta, 64);
-    hi = __shfl_down(hi, delta, 64);
-    return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double nt_shfl_f64(double v, int src) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl(lo, src, 64);
-    hi = __shfl(hi, src, 64);
-    return __hiloint2double(hi, lo);
-}
-
-// alpha and dist * exp(-s dist) of sample i (i < S) as the forward kernel computes alpha
-struct NtSample {
-    float alpha, dalpha;   // dalpha = d alpha / d raw_sigma (0 where the relu is closed)
-    bool closed;           // raw_sigma + noise <= 0 (false for a NaN)
-};
-__device__ __forceinline__ NtSample nt_sample(const float* __restrict__ zr, const float* __restrict__ noise_r, float raw_sigma, int i,
-                                              int S, float norm) {
-    float dist = (i < S - 1) ? (zr[i + 1] - zr[i]) : 1e10f;   // dists = cat(z[1:] - z[:-1], 1e10)
-    dist = dist * norm;
-    const float pre = noise_r ? raw_sigma + noise_r[i] : raw_sigma;
-    const float sig = (pre != pre) ? pre : fmaxf(pre, 0.0f);  // F.relu: a NaN stays a NaN (fmaxf alone returns the 0)
-    const float e = expf(-sig * dist);
-    NtSample o;
-    o.alpha = 1.0f - e;
-    o.closed = pre <= 0.0f;                                   // threshold_backward: 0 where x <= 0, the gradient elsewhere (NaN included)
-    o.dalpha = o.closed ? 0.0f : dist * e;                    // NaN where pre is
-    return o;
-}
 
 __global__ __launch_bounds__(256) void nerf_raw2outputs_backward_kernel(const float* __restrict__ raw, const float* __restrict__ z,
                                                                         const float* __restrict__ rays_d,
@@ -78,8 +39,7 @@ __global__ __launch_bounds__(256) void nerf_raw2outputs_backward_kernel(const fl
     const float* nr = noise ? noise + (size_t)ray * S : nullptr;
     const float* rr = raw + (size_t)ray * S * 4;
     float* gr = g_raw + (size_t)ray * S * 4;
-    const float dx = rays_d[(size_t)ray * 3 + 0], dy = rays_d[(size_t)ray * 3 + 1], dz = rays_d[(size_t)ray * 3 + 2];
-    const float norm = sqrtf(__fadd_rn(__fadd_rn(dx * dx, dy * dy), dz * dz));
+    const float norm = ray_norm(rays_d, ray);
     const float g0 = g_rgb_map[(size_t)ray * 3 + 0], g1 = g_rgb_map[(size_t)ray * 3 + 1], g2 = g_rgb_map[(size_t)ray * 3 + 2];
     const float gsum = white_bkgd ? (g0 + g1) + g2 : 0.0f;
     const int n_chunk = (S + 63) >> 6;
@@ -91,19 +51,14 @@ __global__ __launch_bounds__(256) void nerf_raw2outputs_backward_kernel(const fl
         const bool ok = i < S;
         double pterm = 1.0;
         if (ok) {
-            const NtSample sm = nt_sample(zr, nr, rr[(size_t)i * 4 + 3], i, S, norm);
+            const ScanSample sm = scan_sample(zr, nr, rr[(size_t)i * 4 + 3], i, S, norm);
             pterm = (double)((1.0f - sm.alpha) + 1e-10f);
         }
-        double incl = pterm;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const double u = nt_shfl_up_f64(incl, d);
-            if (lane >= d) incl *= u;
-        }
-        double excl = nt_shfl_up_f64(incl, 1);
+        const double incl = wave_scan_mul(pterm, lane);
+        double excl = shfl_up_f64(incl, 1);
         if (lane == 0) excl = 1.0;
         if (ok) gr[(size_t)i * 4 + 3] = (float)(carry * excl);
-        carry *= nt_shfl_f64(incl, 63);
+        carry *= shfl_f64(incl, 63);
     }
 
     // pass 2: E_i = alpha_i q_i + p_i E_{i+1}, E_S = 0; B_i = E_{i+1}
@@ -112,32 +67,32 @@ __global__ __launch_bounds__(256) void nerf_raw2outputs_backward_kernel(const fl
         const int i = k * 64 + lane;
         const bool ok = i < S;
         f32x4 r4 = {0.f, 0.f, 0.f, 0.f};
-        NtSample sm = {0.f, 0.f, true};
+        ScanSample sm = {0.f, 0.f, true};
         float T = 0.f, c0 = 0.f, c1 = 0.f, c2 = 0.f, q = 0.f;
         double a = 0.0, p = 1.0;               // the identity map on the lanes behind the ray's end
         if (ok) {
             r4 = *reinterpret_cast<const f32x4*>(rr + (size_t)i * 4);
-            sm = nt_sample(zr, nr, r4[3], i, S, norm);
+            sm = scan_sample(zr, nr, r4[3], i, S, norm);
             T = gr[(size_t)i * 4 + 3];         // this lane's own store of pass 1
-            c0 = 1.0f / (1.0f + expf(-r4[0]));
-            c1 = 1.0f / (1.0f + expf(-r4[1]));
-            c2 = 1.0f / (1.0f + expf(-r4[2]));
+            c0 = scan_sigmoid(r4[0]);
+            c1 = scan_sigmoid(r4[1]);
+            c2 = scan_sigmoid(r4[2]);
             q = ((g0 * c0 + g1 * c1) + g2 * c2) - gsum;
             a = (double)sm.alpha * (double)q;
             p = (double)((1.0f - sm.alpha) + 1e-10f);
         }
 #pragma unroll
         for (int d = 1; d < 64; d <<= 1) {     // (a, p) of lane l := the map of samples l .. min(l + 2d - 1, 63) of the chunk
-            const double a2 = nt_shfl_down_f64(a, d), p2 = nt_shfl_down_f64(p, d);
+            const double a2 = shfl_down_f64(a, d), p2 = shfl_down_f64(p, d);
             if (lane + d < 64) {
                 a = a + p * a2;
                 p = p * p2;
             }
         }
         const double E = a + p * e_behind;
-        double B = nt_shfl_down_f64(E, 1);
+        double B = shfl_down_f64(E, 1);
         if (lane == 63) B = e_behind;
-        e_behind = nt_shfl_f64(E, 0);
+        e_behind = shfl_f64(E, 0);
         if (ok) {
             const float w = sm.alpha * T;
             const float g_alpha = T * (float)((double)q - B);

@@ -40,6 +40,39 @@ def poison_positions(S):
     return sorted({p for p in (0, 63, 64, S - 1) if p < S})
 
 
+def poison_sample(bad, ray, p, kind, j=0):
+    """poison `kind` of KINDS at sample p of ray `ray` of the case `bad` (scan_case's dict), in place (S >= 2 for
+    kind d); j picks one of the three values of kind j"""
+    S = bad['z'].shape[1]
+    if kind == 'a':
+        bad['raw'][ray, p, 3] = NAN
+    elif kind == 'b':
+        bad['noise'][ray, p] = NAN
+    elif kind == 'c':                       # on a positive interval: the depths are distinct, the last interval is 1e10
+        bad['raw'][ray, p, 3] = INF
+    elif kind == 'd':                       # a zero-length interval: not the last sample's, which is 1e10 long
+        p = min(p, S - 2)
+        bad['raw'][ray, p, 3] = INF
+        bad['z'][ray, p + 1] = bad['z'][ray, p]
+    elif kind == 'e':
+        bad['raw'][ray, p, 3] = -INF
+    elif kind == 'f':
+        bad['raw'][ray, p, p % 3] = NAN
+    elif kind == 'g':
+        bad['raw'][ray, p, 0] = INF
+        bad['raw'][ray, p, 1] = -INF
+    elif kind == 'h':
+        bad['z'][ray, p] = NAN
+    elif kind == 'i':
+        bad['rd'][ray] = 0.
+    elif kind == 'j':
+        bad['rd'][ray, p % 3] = (NAN, INF, -INF)[j % 3]
+        bad['raw'][ray, p, 3] = -1.                  # a closed sample: 0 * |inf| is a NaN (open ones alone give alpha = 1, all finite)
+    elif kind == 'k':
+        bad['raw'][ray, p, 3] = INF
+        bad['rd'][ray] = 0.
+
+
 def scan_case(n, S, kind, white, with_noise):
     """(clean, poisoned): two dicts raw [n,S,4], z [n,S], rd [n,3], noise [n,S] or None, g_rgb [n,3]; the poisoned one differs on the
     odd rays only.  Kind b (NaN in the noise alone) without a noise tensor has no case: None."""
@@ -61,33 +94,7 @@ def scan_case(n, S, kind, white, with_noise):
         p = pos[j % len(pos)] if n > 1 else pos[len(pos) // 2]
         if n == 5:
             p = (pos[0], pos[-1])[j % 2]
-        if kind == 'a':
-            bad['raw'][ray, p, 3] = NAN
-        elif kind == 'b':
-            bad['noise'][ray, p] = NAN
-        elif kind == 'c':                       # on a positive interval: the depths are distinct, the last interval is 1e10
-            bad['raw'][ray, p, 3] = INF
-        elif kind == 'd':                       # a zero-length interval: not the last sample's, which is 1e10 long
-            p = min(p, S - 2)
-            bad['raw'][ray, p, 3] = INF
-            bad['z'][ray, p + 1] = bad['z'][ray, p]
-        elif kind == 'e':
-            bad['raw'][ray, p, 3] = -INF
-        elif kind == 'f':
-            bad['raw'][ray, p, p % 3] = NAN
-        elif kind == 'g':
-            bad['raw'][ray, p, 0] = INF
-            bad['raw'][ray, p, 1] = -INF
-        elif kind == 'h':
-            bad['z'][ray, p] = NAN
-        elif kind == 'i':
-            bad['rd'][ray] = 0.
-        elif kind == 'j':
-            bad['rd'][ray, p % 3] = (NAN, INF, -INF)[j % 3]
-            bad['raw'][ray, p, 3] = -1.                  # a closed sample: 0 * |inf| is a NaN (open ones alone give alpha = 1, all finite)
-        elif kind == 'k':
-            bad['raw'][ray, p, 3] = INF
-            bad['rd'][ray] = 0.
+        poison_sample(bad, ray, p, kind, j)
     return clean, bad
 
 

@@ -316,7 +316,7 @@ def test_teacher_auto_precision_is_measured(pkg):
         eng.close()
 
 
-@pytest.mark.parametrize('S0,NI,white', [(64, 128, True), (64, 64, False), (17, 33, True), (3, 5, False)])
+@pytest.mark.parametrize('S0,NI,white', [(64, 128, True), (64, 64, False), (17, 33, True), (3, 5, False), (64, 192, True), (3, 1, False)])
 def test_fused_coarse_scan_equals_the_three_launches(pkg, S0, NI, white):
     """The deterministic path runs raw2outputs(coarse) + sample_pdf + merge as ONE launch (nerf_coarse_scan_kernel); with
     nerf_debug_set_split_scans the same context runs the three stand-alone kernels: every output of render_rays and every extra

@@ -135,6 +135,29 @@ def test_scan_backward_against_float64(L, S):
                 assert gap_hip <= 4 * gap_t32
 
 
+@pytest.mark.parametrize('S', [64, 65])
+def test_scan_backward_chunk_carry_against_float64(L, S):
+    """One full chunk, and one sample into the second: T of sample 64 is pass 1's carry (the product scan the forward kernels
+    share) and B of sample 63 is pass 2's.  Five rays (a second block with one live wave), with noise: g_raw within 4 x
+    torch-fp32's gap from float64 autograd, as test_scan_backward_against_float64 holds it."""
+    from oracle import r2l_oracle as O
+    n = 5
+    for kind in ('thin', 'mixed'):
+        for white in (False, True):
+            seed = 900 + S * 4 + 2 * white + (kind == 'mixed')
+            raw, z, rd, g_rgb = _scan_case(n, S, kind, seed)
+            noise = torch.randn(n, S, generator=torch.Generator().manual_seed(seed + 1))
+            got, margins = _scan_hip(L, raw, z, rd, g_rgb, white, noise)
+            ref = _scan_autograd(O, raw, z, rd, g_rgb, white, noise, torch.float64)
+            t32 = _scan_autograd(O, raw, z, rd, g_rgb, white, noise, torch.float32)
+            gap_hip, gap_t32 = _rel(got, ref), _rel(t32, ref)
+            if not np.isfinite(gap_t32):
+                gap_t32 = float('inf')
+            print(f'S={S} {kind} white={white}: relative L2 gap from float64: HIP {gap_hip:.2e}, torch fp32 {gap_t32:.2e}')
+            assert torch.isfinite(got).all() and torch.isnan(margins).all()
+            assert gap_hip <= 4 * gap_t32
+
+
 def test_scan_backward_one_sample_matches_the_forward_kernel(L, pkg):
     """S = 1: the yardstick's forward (the oracle's expressions with the 1e10 column written out) is what nerf_raw2outputs computes"""
     from efficient_nerf_amd.teacher import raw2outputs
