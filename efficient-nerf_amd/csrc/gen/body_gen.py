@@ -47,11 +47,11 @@ import sys
 
 import numpy as np
 
-from isa import (ACT_EXP, Ins, State, Filler, vr, ar, vreg, areg, sreg, mfma32_16, mfma32_6, ds_read_b128,
+import isa
+from isa import (ACT_EXP, Ins, State, Filler, Sched, ListSched, OptsBase, vr, ar, vreg, areg, sreg, mfma32_16, mfma32_6, ds_read_b128,
                  ds_read_b64, ds_read_b96, ds_max_u32, ds_write_b128, ds_write_b64, v_max3_abs, mfma32_8, v_cvt_pk_fp8_f16,
                  f_to_e4m3, v_mul_lit, v_fmac_lit, global_load_x4_a, ds_write_b128_stage, v_lshl_or, v_sub_imm, v_lshl_imm, waitcnt_lgkm, waitcnt_vm, barrier, valu, v_max0, v_accr, v_accw, v_cvt_pk_f16, v_resid16,
-                 v_cvt_pk32_bf6, s_nop, salu, f_to_bf6, pack6, layer_exponent, weight_exps, f32_bits, check_hazards_stream,
-                 model_cycles)
+                 v_cvt_pk32_bf6, s_nop, salu, f_to_bf6, pack6, layer_exponent, weight_exps, f32_bits)
 
 # ---------------------------------------------------------------------------------------------
 # register map
@@ -65,6 +65,7 @@ V_L0 = 226        # lane*16                (LDS bytes 0 .. 65535)
 V_L1 = 227        # lane*16 + 65536
 V_L8A = 228       # lane*8                 (8-byte parts of the bf6 operands)
 V_L8B = 229       # lane*8 + 65536
+L_BASES = (V_L0, V_L1, V_L8A, V_L8B)
 V_AUX = 230       # LDS aux base + (lane>>5)*16 (+4096 on odd blocks)
 V_DMAOFF = 231    # wave*7168 + lane*16    (pieces 0..3; V_DMAOFF2 = +4096: pieces 4..6)
 V_DMAOFF2 = 232
@@ -152,8 +153,8 @@ DMA6 = False      # --dma6 (bf6r): a wave's share as 6 x dwordx4, the sixth over
 def set_ring(opts):
     """the deep rings and the staged transfer want the same free AGPRs of the bf6 build"""
     global DEEP_RING, STAGE_ON
-    STAGE_ON = bool(getattr(opts, 'stage', False))
-    DEEP_RING = not (STAGE_ON or getattr(opts, 'shallow_ring', False))
+    STAGE_ON = bool(opts.stage)
+    DEEP_RING = not (STAGE_ON or opts.shallow_ring)
 
 
 def configure(fmt):
@@ -475,13 +476,6 @@ def slot_of(T):
     return T % NSLOT
 
 
-def lds_addr(slot, byte_off, width):
-    """(base VGPR, immediate offset) of byte `byte_off` of ring slot `slot` for a per-lane width of 16 or 8 bytes"""
-    off = slot * SLOT + byte_off
-    lo, hi = (V_L0, V_L1) if width == 16 else (V_L8A, V_L8B)
-    return (lo, off) if off < 65536 else (hi, off - 65536)
-
-
 ORDER_BASE = 'tail'   # 'tail': the 16 fp16 MFMAs of a row tile, then its 8 K=64 MFMAs; 'mix': the K=64 ones behind k-steps
                       # 8..15; bf6r always runs 'group': per K=64 step t its four fp16 MFMAs, then (1, t), then (0, t)
 ORDER = ORDER_BASE
@@ -629,37 +623,6 @@ def read_act(tag):
     return ds_read_b96(V_ACT, V_AUX, AUX_ACT, tag=tag)
 
 
-class Sched:
-    """instruction list of consecutive block iterations; tracks the LDS reads for the counted lgkmcnt waits"""
-
-    def __init__(self, opts):
-        self.o = opts
-        self.out = []             # (iteration, Ins)
-        self.ds_issued = 0        # LDS reads issued so far (global count)
-        self.ds_done = 0          # all LDS reads with index < ds_done are known complete
-        self.ds_index = {}        # key -> index of its ds_read
-
-    def emit(self, it, ins):
-        self.out.append((it, ins))
-        if ins.kind == 'ds':
-            self.ds_issued += 1
-
-    def need(self, it, key, also=()):
-        """make sure the LDS read registered under `key` has landed; reads in `also` that have been issued by now ride along
-        (one s_waitcnt for a run of MFMAs: the instruction itself holds the wave's issue for some cycles, needed or not)"""
-        if key not in self.ds_index and it == 0:
-            return  # issued by the iteration before the schedule starts (iteration 0 is never the extracted one)
-        idx = self.ds_index[key]
-        if idx < self.ds_done:
-            return
-        for k2 in also:
-            if k2 in self.ds_index:
-                idx = max(idx, self.ds_index[k2])
-        n = min(15, self.ds_issued - idx - 1)         # the counter has 4 bits; waiting for more is always right
-        self.emit(it, waitcnt_lgkm(n))
-        self.ds_done = self.ds_issued - n
-
-
 def build_fillers(it, opts):
     """fillers of block iteration `it` (anchors numbered it*384 + ...)"""
     F = []
@@ -698,7 +661,7 @@ def build_fillers(it, opts):
             deadline = A(T, 'm16', s_)
             if FMT == 'f16':   # hi(W) of k-step s feeds two MFMAs; a second ring streams lo(W)
                 earliest = max(A(prev // 16, 'mhl', prev % 16), A(T, 'm16', s_) - 3 * opts.rd_lead)
-                bv, off = lds_addr(slot, off_lo(s_), 16)
+                bv, off = isa.lds_addr(SLOT, L_BASES, slot, off_lo(s_), 16)
                 F.append(Filler(ds_read_b128(V_HL + 4 * (n % NHI), bv, off, tag=('hl', it, T, s_)),
                                 max(A(prev // 16, 'mlh', prev % 16), A(T, 'mlh', s_) - 3 * opts.rd_lead), A(T, 'mlh', s_), ('rdl',)))
             if WREG:
@@ -707,7 +670,7 @@ def build_fillers(it, opts):
                 TP, tp = prev // 16, (prev % 16) >> 2
                 earliest = max(A(TP, 'm16', prev % 16), cvt_window(TP, tp)[1], A(T, 'm16', s_) - opts.rd_lead - 4)
                 deadline = min(deadline, cvt_window(T, s_ >> 2)[0])
-            bv, off = lds_addr(slot, off_hi(s_), 16)
+            bv, off = isa.lds_addr(SLOT, L_BASES, slot, off_hi(s_), 16)
             fl, rg = HIF(n % NHI)
             F.append(Filler(ds_read_b128(rg, bv, off, tag=('hi', it, T, s_), dfile=fl), earliest, deadline, ('rd',)))
         for j in range(8):
@@ -725,20 +688,20 @@ def build_fillers(it, opts):
             deadline = A(T, 'm6', j)
             o1, o2 = off_a6(j)
             fl, reg = A6(n % NA6B)
-            bv, off = lds_addr(slot, o1, 16)
+            bv, off = isa.lds_addr(SLOT, L_BASES, slot, o1, 16)
             F.append(Filler(ds_read_b128(reg, bv, off, tag=('a6', it, T, j, 0), dfile=fl), earliest, deadline, ('rd6',)))
             if FMT == 'bf6':
-                bv, off = lds_addr(slot, o2, 8)
+                bv, off = isa.lds_addr(SLOT, L_BASES, slot, o2, 8)
                 F.append(Filler(ds_read_b64(reg + 4, bv, off, tag=('a6', it, T, j, 1), dfile=fl), earliest, deadline, ('rd6',)))
             else:
-                bv, off = lds_addr(slot, o2, 16)
+                bv, off = isa.lds_addr(SLOT, L_BASES, slot, o2, 16)
                 F.append(Filler(ds_read_b128(reg + 4, bv, off, tag=('a6', it, T, j, 1)), earliest, deadline, ('rd6',)))
         if WREG:
             # bf6(W / 2^(e-4)) of K=64 step t from the four fragments the wave holds for its own fp16 MFMAs: after the last of
             # them has landed and the previous conversion's MFMA has read the operand register; two instructions before its MFMA
             for t in range(4):
                 e, d = cvt_window(T, t)
-                if 'wcvt' in getattr(opts, 'drop', ()):       # diagnostics (wrong results): what the conversions cost
+                if 'wcvt' in opts.drop:       # diagnostics (wrong results): what the conversions cost
                     continue
                 F.append(Filler(v_cvt_pk32_bf6(V_WCV, HI(4 * (t & 1)), V_WSC + layer), e, d, ('wcv',), needs=(('hi', it, T, 4 * t + 3),)))
         if T == 8:
@@ -813,14 +776,9 @@ def build_fillers(it, opts):
                 seq.append(stage_write(i, (T + 2) % NSLOT, tag=('stw', it, T, i)))
                 seq.append(stage_load(i, tag=('dma', it, T, i)))
         else:
-            seq.append(salu('s_mov_b32 m0, %s' % sreg(S_M0SLOT + tgt_slot),
-                            lambda st, k=S_M0SLOT + tgt_slot: setattr(st, 'm0', st.S[k])))
-            seq.append(s_nop(0))
-            for i in range(PW):
-                if i == 4:
-                    seq.append(salu('s_add_u32 m0, m0, 0x1000', lambda st: setattr(st, 'm0', st.m0 + 4096)))
-                    seq.append(s_nop(0))
-                seq.append(dma_piece(i, tag=('dma', it, T, i)))
+            seq += isa.dma_pieces(salu('s_mov_b32 m0, %s' % sreg(S_M0SLOT + tgt_slot),
+                                       lambda st, k=S_M0SLOT + tgt_slot: setattr(st, 'm0', st.S[k])),
+                                  [dma_piece(i, tag=('dma', it, T, i)) for i in range(PW)])
         end = a0 + ANCH_PER_TILE - ANCH_PER_TILE // 12      # well before the next rendezvous
         if opts.dma_burst:
             for ins in seq:
@@ -847,20 +805,11 @@ def schedule(opts, n_iter=3):
     position's iteration is that of the surrounding anchors"""
     set_ring(opts)
     configure(opts.fmt)
-    sch = Sched(opts)
+    sch = Sched()
     fillers = []
     for it in range(n_iter):
         fillers += build_fillers(it, opts)
-    for i, f in enumerate(fillers):
-        f.seq = i
-    chains = {}
-    for f in fillers:
-        chains.setdefault(f.chain, []).append(f)
-    for ch in chains.values():
-        ch.sort(key=lambda f: (f.seq,))
-        for i in range(len(ch) - 2, -1, -1):   # a filler must not hold up a successor with an earlier deadline
-            ch[i].deadline = min(ch[i].deadline, ch[i + 1].deadline)
-    heads = {ch: 0 for ch in chains}
+    ls = ListSched(fillers, sch)
     deep = FMT == 'bf6' and not WREG and DEEP_RING
     # with the deep rings the reads run far enough ahead for one wait to cover a short run of MFMAs (-1 % on top of the rings' -1 %)
     wg16 = opts.wait_group if opts.wait_group is not None else (3 if deep else 2 if FMT in ('fp8', 'f16') else 1)
@@ -869,64 +818,38 @@ def schedule(opts, n_iter=3):
     total_anchors = n_iter * per_block
     anchors = tile_anchors()
 
-    def ready(pos):
-        """chain heads that may issue at anchor position pos, by deadline"""
-        r = []
-        for ch, lst in chains.items():
-            i = heads[ch]
-            if i < len(lst) and lst[i].earliest <= pos:
-                r.append(lst[i])
-        r.sort(key=lambda f: (f.deadline, f.seq))
-        return r
-
-    def issue(f, it):
-        ins = f.ins
-        for key in f.needs:
-            sch.need(it, key)
-        if ins.kind == 'ds':
-            sch.ds_index[ins.tag] = sch.ds_issued
-        sch.emit(it, ins)
-        heads[f.chain] += 1
-
-    while True:  # pre-region: the prefetch of tile 0 of iteration 0
-        r = ready(-1)
-        if not r:
-            break
-        issue(r[0], -1)
+    sch.it = -1
+    ls.start()   # pre-region: the prefetch of tile 0 of iteration 0
 
     for a in range(total_anchors):
-        it = a // per_block
+        it = sch.it = a // per_block
         T = (a // ANCH_PER_TILE) % TILES
         kind, sj = anchors[a % ANCH_PER_TILE]
-        while True:  # forced fillers: deadline reached
-            r = [f for f in ready(a - 1) if f.deadline <= a]
-            if not r:
-                break
-            issue(r[0], it)
+        ls.due(a)
         layer, u = T >> 3, T & 7
         hset = INH if layer == 0 else HH
         if a % per_block == 0:
             # loop head: the prefetch issued by the previous iteration's tail -- or by the prologue, which lacks the
             # tail's other reads, so a counted wait would be too generous there -- is drained completely
-            sch.emit(it, waitcnt_lgkm(0))
-            sch.ds_done = sch.ds_issued
+            sch.emit(waitcnt_lgkm(0))
+            sch.landed()
             if WREG:   # f32 divisor 2^(e-4) of this block's layer-1 conversions, from the E8M0 byte its MFMAs use
                 for ins in derive_wsc(V_WSC, V_SC + 1):
-                    sch.emit(it, ins)
+                    sch.emit(ins)
         if WREG and a % ANCH_PER_TILE == 0 and T == 2:
-            sch.need(it, ('scale', it, 1))          # ... and of its layer-2 conversions (tiles 8..15; scales read during tile 1)
+            sch.need(('scale', it, 1))          # ... and of its layer-2 conversions (tiles 8..15; scales read during tile 1)
             for ins in derive_wsc(V_WSC + 1, V_SC + 3):
-                sch.emit(it, ins)
+                sch.emit(ins)
         if FMT != 'f16' and a % ANCH_PER_TILE == 0 and T == 1:
             # layer 2 of the previous block and its last epilogue are over: the exponents of this block's H set (layer 2
             # consumes it) and of the set layer 2 produces
             for ins in derive_sb(V_SB + 2, V_ACT + 1) + derive_cv(V_CVD + 2, V_ACT + 2):
-                sch.emit(it, ins)
+                sch.emit(ins)
         if FMT != 'f16' and a % ANCH_PER_TILE == 0 and T == 9:
             # layer 1 and its last epilogue are over: the next block's exponents (read behind the aux flip of tile 8)
-            sch.need(it, ('act', it + 1))
+            sch.need(('act', it + 1))
             for ins in derive_sb(V_SB, V_ACT) + derive_cv(V_CVD, V_ACT + 1):
-                sch.emit(it, ins)
+                sch.emit(ins)
         dfile, d = ('v', ACC(T & 1)) if layer == 0 or FMT == 'f16' else ('a', X(u))
         if kind in ('mhl', 'mlh'):      # f16: hi(W) x lo(a) | lo(W) x hi(a)
             n = T * 16 + sj
@@ -934,14 +857,14 @@ def schedule(opts, n_iter=3):
                 lset = A_INL if layer == 0 else A_HLO
                 ins = mfma32_16(dfile, d, HI(n % NHI), lset + 4 * sj, dfile, d, tag=(kind, it, T, sj), bfile='a')
             else:
-                sch.need(it, ('hl', it, T, sj))
+                sch.need(('hl', it, T, sj))
                 ins = mfma32_16(dfile, d, V_HL + 4 * (n % NHI), hset(sj), dfile, d, tag=(kind, it, T, sj))
             cap = opts.cap16
         elif kind == 'm16':
-            sch.need(it, ('hi', it, T, sj), [('hi', it, T, sj + g) for g in range(1, wg16) if sj + g < 16])
+            sch.need(('hi', it, T, sj), [('hi', it, T, sj + g) for g in range(1, wg16) if sj + g < 16])
             n = T * 16 + sj
             if layer == 0 and sj == 0:
-                sch.need(it, ('bias', it, T, 3))
+                sch.need(('bias', it, T, 3))
                 fl, rg = HIF(n % NHI)
                 ins = mfma32_16('v', d, rg, hset(sj), 'v', d if WREG else V_BIAS, tag=('m16', it, T, sj), afile=fl)
             elif FMT == 'f16' and sj == 0:      # layer 2: a fresh accumulator (its bias is folded into later layer-1 biases)
@@ -954,11 +877,11 @@ def schedule(opts, n_iter=3):
             term, t = J_ORDER[sj]
             n = T * 4 + t if WREG else T * 8 + sj
             if in_stream(sj):
-                sch.need(it, ('a6', it, T, sj, 1), [('a6', it, T, sj + g, 1) for g in range(1, wg6) if sj + g < 8])
+                sch.need(('a6', it, T, sj, 1), [('a6', it, T, sj + g, 1) for g in range(1, wg6) if sj + g < 8])
             if u == 0 and (kind, sj) == [x for x in anchors if x[0] == 'm6'][0]:
-                sch.need(it, ('scale', it, layer))
+                sch.need(('scale', it, layer))
             if sj == 0 and ORDER == 'tail' and opts.chain_nop >= 0:
-                sch.emit(it, s_nop(opts.chain_nop))      # fp16 -> scaled MFMA on one accumulator: keep them apart
+                sch.emit(s_nop(opts.chain_nop))      # fp16 -> scaled MFMA on one accumulator: keep them apart
             b6 = A_IN6 if layer == 0 else A_H6
             if FMT == 'fp8':
                 ins = mfma32_8(dfile, d, A6(n % NA6B)[1], B6(b6, term, t), V_SC + 2 * layer + term, V_SB + 2 * layer + term,
@@ -969,19 +892,13 @@ def schedule(opts, n_iter=3):
                                tag=('m6', it, T, sj), afile=fl)
             cap = opts.cap6 * (1 if FMT == 'bf6' else 2)    # a 64-cycle MFMA shadows twice the issue slots
         if not (kind == 'm6' and J_ORDER[sj][0] in opts.skip_terms):
-            sch.emit(it, ins)
-        budget = cap
-        while budget > 0:
-            r = ready(a)
-            if not r:
-                break
-            issue(r[0], it)
-            budget -= r[0].ins.cost
-    return sch.out
+            sch.emit(ins)
+        ls.fill(a, cap)
+    return list(zip(sch.its, sch.out))
 
 
-class Opts:
-    def __init__(self, **kw):
+class Opts(OptsBase):
+    def declare(self):
         self.rd_lead = 4          # anchors (MFMAs of 32 cycles) an fp16 fragment read is issued ahead of its MFMA, at most
         self.rd_lead6 = 4
         self.cap16 = 6            # issue slots for fillers behind an MFMA
@@ -997,7 +914,7 @@ class Opts:
         self.wait_group6 = None   # ... K=64 operands; None: 2 with the deep rings, else 1
         self.rdv_at = None        # anchor of a row tile in front of which its rendezvous sits (None: a third into the tile)
         self.shallow_ring = False # bf6: fragment / operand rings of 4 / 2 buffers in VGPRs only (the round-2 kernel)
-        self.__dict__.update(kw)
+        self.drop = ()            # diagnostics only (wrong results): timing knock-outs of instruction classes (--drop)
 
 
 def act_prologue():
@@ -1198,14 +1115,9 @@ def kernel_text(opts):
              's_addc_u32 %s, %s, 0' % (sreg(S_G + 1), sreg(S_W + 1)),
              's_add_u32 %s, %s, 0x%x' % (sreg(S_POS), sreg(S_POS), CHUNK),
              's_cmp_eq_u32 %s, %s' % (sreg(S_POS), sreg(S_END)),
-             's_cselect_b32 %s, 0, %s' % (sreg(S_POS), sreg(S_POS)),
-             's_mov_b32 m0, %s' % sreg(S_M0SLOT + slot),
-             's_nop 0']
-        for i in range(PW):
-            if i == 4:
-                r += ['s_add_u32 m0, m0, 0x1000', 's_nop 0']
-            r.append(dma_piece(i).text)
-        return r
+             's_cselect_b32 %s, 0, %s' % (sreg(S_POS), sreg(S_POS))]
+        pieces = isa.dma_pieces(salu('s_mov_b32 m0, %s' % sreg(S_M0SLOT + slot)), [dma_piece(i) for i in range(PW)])
+        return r + [ins.text for ins in pieces]
 
     # tail table -> LDS (4 KiB, 1 KiB per wave; the oldest load of the kernel: landed with the first chunk)
     a('s_add_u32 m0, %s, 0x%x' % (sreg(S_T0 + 1), LDS_TAIL))
@@ -1235,14 +1147,14 @@ def kernel_text(opts):
     a('s_add_u32 %s, %s, %s' % (sreg(S_T0 + 4), sreg(S_XIN), sreg(S_TILEOFF)))
     a('s_addc_u32 %s, %s, %s' % (sreg(S_T0 + 5), sreg(S_XIN + 1), sreg(S_TILEOFF + 1)))
     for i in range(32):
-        if 'xload' in getattr(opts, 'drop', ()):      # diagnostics (wrong results): what the exposed x load of a ray tile costs
+        if 'xload' in opts.drop:      # diagnostics (wrong results): what the exposed x load of a ray tile costs
             continue
         a('global_load_dwordx4 %s, %s, %s offset:%d' % (areg(A_X + 4 * i, 4), vreg(V_L0), sreg(S_T0 + 4, 2), (i % 4) * 1024))
         if i % 4 == 3:
             a('s_add_u32 %s, %s, 0x1000' % (sreg(S_T0 + 4), sreg(S_T0 + 4)))
             a('s_addc_u32 %s, %s, 0' % (sreg(S_T0 + 5), sreg(S_T0 + 5)))
     a('s_waitcnt vmcnt(0)')
-    if 'xload2' in getattr(opts, 'drop', ()):      # diagnostics (same results): the x load a second time, exposed like the first
+    if 'xload2' in opts.drop:      # diagnostics (same results): the x load a second time, exposed like the first
         a('s_add_u32 %s, %s, %s' % (sreg(S_T0 + 4), sreg(S_XIN), sreg(S_TILEOFF)))
         a('s_addc_u32 %s, %s, %s' % (sreg(S_T0 + 5), sreg(S_XIN + 1), sreg(S_TILEOFF + 1)))
         for i in range(32):
@@ -1306,7 +1218,7 @@ def kernel_text(opts):
 
 def emit_inc(path, opts):
     L, pro, body = kernel_text(opts)
-    drop = getattr(opts, 'drop', ())   # diagnostics only (wrong results): timing knock-outs of instruction classes
+    drop = opts.drop
     if drop:
         texts = set()
         for ins in body:
@@ -1321,14 +1233,8 @@ def emit_inc(path, opts):
     if 'lgkmnop' in drop:      # every counted LDS wait replaced by an s_nop 0: same instruction count, no waiting (wrong results)
         first = L.index('L_block_%=:')
         L = L[:first + 1] + ['s_nop 0' if t.startswith('s_waitcnt lgkmcnt') else t for t in L[first + 1:]]
-    n = {}
-    for ins in body:
-        n[ins.kind] = n.get(ins.kind, 0) + 1
-    with open(path, 'w') as f:
-        f.write('// GENERATED by gen/body_gen.py -- do not edit.  Loop body (one ResMLP block): %s\n' %
-                ', '.join('%s %d' % kv for kv in sorted(n.items())))
-        for line in L:
-            f.write('"%s\\n\\t"\n' % line)
+    n = isa.kind_counts(body)
+    isa.write_inc(path, 'body_gen.py', 'Loop body (one ResMLP block): ' + isa.counts_text(n), L)
     return n
 
 
@@ -1402,9 +1308,7 @@ def emulate_tile(opts, img, aux, x_tile_regs, n_block, wave=0, check_hazards=Tru
     waitcnt_lgkm(0).emu(st)
     if FMT == 'f16':
         st.run(f16_join_ops(7, 1))
-    errs = list(st.errors)
-    if check_hazards:
-        errs += check_hazards_stream(body + body)
+    errs = isa.emulation_errors(st, [body + body] if check_hazards else [])
     if opts.guard:   # the maxima rows (f32) of the 2 n_block operand sets ride along
         return st.A[A_X:A_X + 128].view(np.float32).copy(), errs, st.lds[LDS_GSTAT:LDS_GSTAT + 2 * n_block * GSTAT_ROW].view(np.float32).reshape(2 * n_block, 32).copy()
     return st.A[A_X:A_X + 128].view(np.float32).copy(), errs
@@ -1454,10 +1358,7 @@ def main():
         print('wrote', a.emit, n)
     if a.dump:
         pro, body = steady_block(opts)
-        with open(a.dump, 'w') as f:
-            for ins in body:
-                f.write(ins.text + '\n')
-        print('model cycles per block', model_cycles(body))
+        isa.dump_stream(a.dump, body, 'block')
 
 
 configure('bf6')

@@ -33,9 +33,9 @@ import sys
 import numpy as np
 
 import isa
-from isa import (Ins, State, Filler, vr, ar, vreg, areg, sreg, mfma32_16, mfma32_6, ds_read_b128, ds_read_b64, waitcnt_lgkm,
-                 waitcnt_vm, barrier, valu, v_max0, v_accr, v_cvt_pk_f16, v_resid16, v_cvt_pk32_bf6, s_nop, salu, f_to_bf6,
-                 pack6, layer_exponent, weight_exps, f32_bits, check_hazards_stream, model_cycles, v_f32_op, v_fma_f32,
+from isa import (Ins, State, Filler, Sched, ListSched, OptsBase, vr, ar, vreg, areg, sreg, mfma32_16, mfma32_6, ds_read_b128,
+                 ds_read_b64, waitcnt_lgkm, waitcnt_vm, barrier, valu, v_max0, v_accr, v_cvt_pk_f16, v_resid16, v_cvt_pk32_bf6,
+                 s_nop, salu, f_to_bf6, pack6, layer_exponent, weight_exps, f32_bits, model_cycles, v_f32_op, v_fma_f32,
                  v_ldexp_f32, v_rndne_f32, v_sin_f32, v_max3_abs)
 
 # ---------------------------------------------------------------------------------------------
@@ -52,6 +52,7 @@ V_LO = 136         # 136..151: fp16 residual pairs
 V_HI = 152         # 152..183: fp16 weight fragments, 8 buffers
 V_A6 = 184         # 184..195: bf6 weight operands, 2 buffers x 6
 V_L0, V_L1, V_L8A, V_L8B, V_AUX, V_LOFF, V_LANE, V_ST = 196, 197, 198, 199, 200, 201, 202, 203
+L_BASES = (V_L0, V_L1, V_L8A, V_L8B)
 V_SBA, V_SBL, V_CVA, V_CVL = 204, 205, 206, 207
 V_SC = 208         # 208, 209: E8M0 weight scales (w - hi | w)
 N_VGPR_CLOBBER = 210
@@ -304,40 +305,21 @@ def anchor(ci, k, kind, sj):
     return ci * ANCH_PER_CHUNK + k * 6 + (sj if kind == 'm16' else 4 + sj)
 
 
-def lds_addr(slot, byte_off, width):
-    off = slot * CHUNK + byte_off
-    lo, hi = (V_L0, V_L1) if width == 16 else (V_L8A, V_L8B)
-    return (lo, off) if off < 65536 else (hi, off - 65536)
-
-
-def chunk_issue_seq(cn):
+def fetch_chunk(cn):
     """SALU + LDS-DMA instructions that fetch chunk cn (wrapped into the tile's stream) into its ring slot"""
-    off = (cn % NCH) * CHUNK
-    slot = cn % NSLOT
-    seq = [salu('s_add_u32 %s, %s, %s' % (sreg(S_G), sreg(S_W), sreg(S_WPW)), lambda st: st.S.__setitem__(S_G, st.S[S_W] + st.S[S_WPW])),
-           salu('s_addc_u32 %s, %s, 0' % (sreg(S_G + 1), sreg(S_W + 1)))]
-    if off:
-        seq += [salu('s_add_u32 %s, %s, 0x%x' % (sreg(S_G), sreg(S_G), off), lambda st: st.S.__setitem__(S_G, st.S[S_G] + off)),
-                salu('s_addc_u32 %s, %s, 0' % (sreg(S_G + 1), sreg(S_G + 1)))]
-    seq.append(salu('s_add_u32 m0, %s, 0x%x' % (sreg(S_WPW), slot * CHUNK), lambda st: setattr(st, 'm0', st.S[S_WPW] + slot * CHUNK)))
-    seq.append(s_nop(0))
-    for i in range(PW):
-        if i == 4:
-            seq.append(salu('s_add_u32 m0, m0, 0x1000', lambda st: setattr(st, 'm0', st.m0 + 4096)))
-            seq.append(s_nop(0))
-        seq.append(dma_piece(i, tag=('dma', cn, i)))
-    return seq
+    return isa.chunk_issue_seq(S_G, S_W, S_WPW, (cn % NCH) * CHUNK, (cn % NSLOT) * CHUNK,
+                               [dma_piece(i, tag=('dma', cn, i)) for i in range(PW)])
 
 
-class Opts:
-    def __init__(self, **kw):
+class Opts(OptsBase):
+    def declare(self):
         self.rd_lead = 6
         self.rd_lead6 = 5
         self.cap = 7
         self.dma_gap = 1
         self.pair_waits = True    # one lgkmcnt wait for two consecutive fp16 fragments when both reads are out
         self.fmt = 'bf6'
-        self.__dict__.update(kw)
+        self.drop = ()            # (no knock-outs in this generator)
 
 
 def build_fillers(opts):
@@ -352,14 +334,14 @@ def build_fillers(opts):
                 a = anchor(ci, k, 'm16', s)
                 prev = last16.get(n16 - NHI, -1)
                 pc = piece_hi(k, s)
-                bv, off = lds_addr(ci % NSLOT, pc * 1024, 16)
+                bv, off = isa.lds_addr(CHUNK, L_BASES, ci % NSLOT, pc * 1024, 16)
                 cert = -1 if ci < 3 else (ci - 1) * ANCH_PER_CHUNK + HALF + 1
                 F.append(Filler(ds_read_b128(V_HI + (n16 % NHI) * 4, bv, off, tag=('hi', ci, k, s)),
                                 max(prev, a - opts.rd_lead, cert), a, ('rd',)))
                 last16[n16] = anchor(ci, k, 'mhl', s) if FMT == 'f16' else a
                 if FMT == 'f16':      # lo(W) of the same k-step, second ring
                     al = anchor(ci, k, 'mlh', s)
-                    bv, off = lds_addr(ci % NSLOT, (16 + pc) * 1024, 16)
+                    bv, off = isa.lds_addr(CHUNK, L_BASES, ci % NSLOT, (16 + pc) * 1024, 16)
                     F.append(Filler(ds_read_b128(V_HL + (n16 % NHL) * 4, bv, off, tag=('hl', ci, k, s)),
                                     max(last6.get(n16 - NHL, -1), al - opts.rd_lead, cert), al, ('rdl',)))
                     last6[n16] = al
@@ -369,10 +351,10 @@ def build_fillers(opts):
                 prev = last6.get(n6 - 2, -1)
                 cert = -1 if ci < 3 else (ci - 1) * ANCH_PER_CHUNK + HALF + 1
                 e = max(prev, a - opts.rd_lead6, cert)
-                bv, off = lds_addr(ci % NSLOT, piece_a6(k, t) * 1024, 16)
+                bv, off = isa.lds_addr(CHUNK, L_BASES, ci % NSLOT, piece_a6(k, t) * 1024, 16)
                 F.append(Filler(ds_read_b128(V_A6 + (n6 & 1) * 6, bv, off, tag=('a6', ci, k, t, 0)), e, a, ('rd6',)))
                 pc, po = piece_a6b(k, t)
-                bv, off = lds_addr(ci % NSLOT, pc * 1024 + po, 8)
+                bv, off = isa.lds_addr(CHUNK, L_BASES, ci % NSLOT, pc * 1024 + po, 8)
                 F.append(Filler(ds_read_b64(V_A6 + (n6 & 1) * 6 + 4, bv, off, tag=('a6', ci, k, t, 1)), e, a, ('rd6',)))
                 last6[n6] = a
                 n6 += 1
@@ -389,7 +371,7 @@ def build_fillers(opts):
         F.append(Filler(waitcnt_vm(PW if ci >= 1 else 0), ar - 1, ar + 1, ch))
         F.append(Filler(barrier(), ar - 1, ar + 1, ch))
         k = 0
-        for ins in chunk_issue_seq(ci + 3):
+        for ins in fetch_chunk(ci + 3):
             if ins.kind != 'dma' and k == 0:
                 F.append(Filler(ins, ar - 1, ar + 3, ch))
             else:
@@ -399,69 +381,13 @@ def build_fillers(opts):
     return F
 
 
-class Sched:
-    def __init__(self):
-        self.out = []
-        self.ds_issued = 0
-        self.ds_done = 0
-        self.ds_index = {}
-
-    def emit(self, ins):
-        self.out.append(ins)
-        if ins.kind == 'ds':
-            self.ds_index[ins.tag] = self.ds_issued
-            self.ds_issued += 1
-
-    def need(self, key, also=()):
-        """wait for the LDS read `key`; reads in `also` that have been issued ride along (one wait for a run of MFMAs)"""
-        idx = self.ds_index[key]
-        if idx < self.ds_done:
-            return
-        for k2 in also:
-            if k2 in self.ds_index:
-                idx = max(idx, self.ds_index[k2])
-        self.emit(waitcnt_lgkm(self.ds_issued - idx - 1))
-        self.ds_done = idx + 1
-
-
 def schedule(opts):
     sch = Sched()
-    fillers = build_fillers(opts)
-    for i, f in enumerate(fillers):
-        f.seq = i
-    chains = {}
-    for f in fillers:
-        chains.setdefault(f.chain, []).append(f)
-    for ch in chains.values():
-        for i in range(len(ch) - 2, -1, -1):
-            ch[i].deadline = min(ch[i].deadline, ch[i + 1].deadline)
-    heads = {ch: 0 for ch in chains}
-
-    def ready(pos):
-        r = []
-        for ch, lst in chains.items():
-            i = heads[ch]
-            if i < len(lst) and lst[i].earliest <= pos:
-                r.append(lst[i])
-        r.sort(key=lambda f: (f.deadline, f.seq))
-        return r
-
-    def issue(f):
-        sch.emit(f.ins)
-        heads[f.chain] += 1
-
-    while True:
-        r = ready(-1)
-        if not r:
-            break
-        issue(r[0])
+    ls = ListSched(build_fillers(opts), sch)
+    ls.start()
     n16 = n6 = 0
     for a in range(N_ANCH):
-        while True:
-            r = [f for f in ready(a - 1) if f.deadline <= a]
-            if not r:
-                break
-            issue(r[0])
+        ls.due(a)
         ci, rem = divmod(a, ANCH_PER_CHUNK)
         k, j = divmod(rem, ANCH_PER_RT)
         p, u = ci >> 1, 4 * (ci & 1) + k
@@ -489,18 +415,8 @@ def schedule(opts):
                            tag=('m6', ci, k, t), bfile='v')
             n6 += 1
         sch.emit(ins)
-        budget = opts.cap
-        while budget > 0:
-            r = ready(a)
-            if not r:
-                break
-            issue(r[0])
-            budget -= r[0].ins.cost
-    while True:
-        r = ready(N_ANCH + 10 ** 6)
-        if not r:
-            break
-        issue(r[0])
+        ls.fill(a, opts.cap)
+    ls.finish()
     return sch.out
 
 
@@ -601,7 +517,7 @@ def tail_ops():
 def prologue_ops():
     seq = []
     for k in range(3):
-        seq += chunk_issue_seq(k)
+        seq += fetch_chunk(k)
     return seq
 
 
@@ -614,32 +530,17 @@ def emit(dirname, opts):
     configure(opts.fmt)
     setup, _ = setup_ops()
     body = block_stream(opts)
-    n = {}
-    for ins in body:
-        n[ins.kind] = n.get(ins.kind, 0) + 1
-    with open(os.path.join(dirname, NAME + '_asm.inc'), 'w') as f:
-        f.write('// GENERATED by gen/head_gen.py -- do not edit.  Head layer of one 128-ray tile: %s\n' %
-                ', '.join('%s %d' % kv for kv in sorted(n.items())))
-        for line in setup + [i.text for i in body] + ['s_mov_b32 m0, %s' % sreg(S_M0SAVE)]:
-            f.write('"%s\\n\\t"\n' % line)
-    with open(os.path.join(dirname, NAME + '_pro_asm.inc'), 'w') as f:
-        f.write('// GENERATED by gen/head_gen.py -- do not edit.  Ring prologue: chunks 0..2 of the stream\n')
-        pro = ['s_mov_b32 %s, m0' % sreg(S_M0SAVE), 's_mov_b64 %s, %%[wimg]' % sreg(S_W, 2),
-               's_mov_b32 %s, %%[wave]' % sreg(S_WAVE), 's_mul_i32 %s, %s, 0x%x' % (sreg(S_WPW), sreg(S_WAVE), PW * 1024),
-               'v_mbcnt_lo_u32_b32 %s, -1, 0' % vreg(V_LANE), 'v_mbcnt_hi_u32_b32 %s, -1, %s' % (vreg(V_LANE), vreg(V_LANE)),
-               'v_lshlrev_b32 %s, 4, %s' % (vreg(V_L0), vreg(V_LANE)), 'v_add_u32 %s, 0x1000, %s' % (vreg(V_LOFF), vreg(V_L0))]
-        for line in pro + [i.text for i in prologue_ops()] + ['s_mov_b32 m0, %s' % sreg(S_M0SAVE)]:
-            f.write('"%s\\n\\t"\n' % line)
-
-    def clob(vregs, na):
-        regs = ['v%d' % i for i in vregs] + ['a%d' % i for i in range(na)]
-        regs += ['s%d' % i for i in range(N_SGPR_LO, N_SGPR_HI)] + ['vcc', 'scc', 'memory']
-        return ', '.join('"%s"' % r for r in regs) + '\n'
-
-    with open(os.path.join(dirname, NAME + '_clobbers.inc'), 'w') as f:
-        f.write('// GENERATED by gen/head_gen.py: registers the tile block owns\n' + clob(range(N_VGPR_CLOBBER), N_AGPR_CLOBBER))
-    with open(os.path.join(dirname, NAME + '_pro_clobbers.inc'), 'w') as f:
-        f.write('// GENERATED by gen/head_gen.py: registers the ring prologue owns\n' + clob([V_L0, V_LOFF, V_LANE], 0))
+    n = isa.kind_counts(body)
+    gen, sgprs, restore = 'head_gen.py', range(N_SGPR_LO, N_SGPR_HI), ['s_mov_b32 m0, %s' % sreg(S_M0SAVE)]
+    path = os.path.join(dirname, NAME)
+    isa.write_inc(path + '_asm.inc', gen, 'Head layer of one 128-ray tile: ' + isa.counts_text(n), setup + [i.text for i in body] + restore)
+    pro = ['s_mov_b32 %s, m0' % sreg(S_M0SAVE), 's_mov_b64 %s, %%[wimg]' % sreg(S_W, 2),
+           's_mov_b32 %s, %%[wave]' % sreg(S_WAVE), 's_mul_i32 %s, %s, 0x%x' % (sreg(S_WPW), sreg(S_WAVE), PW * 1024),
+           'v_mbcnt_lo_u32_b32 %s, -1, 0' % vreg(V_LANE), 'v_mbcnt_hi_u32_b32 %s, -1, %s' % (vreg(V_LANE), vreg(V_LANE)),
+           'v_lshlrev_b32 %s, 4, %s' % (vreg(V_L0), vreg(V_LANE)), 'v_add_u32 %s, 0x1000, %s' % (vreg(V_LOFF), vreg(V_L0))]
+    isa.write_inc(path + '_pro_asm.inc', gen, 'Ring prologue: chunks 0..2 of the stream', pro + [i.text for i in prologue_ops()] + restore)
+    isa.write_clobbers(path + '_clobbers.inc', gen, 'the tile block owns', range(N_VGPR_CLOBBER), range(N_AGPR_CLOBBER), sgprs)
+    isa.write_clobbers(path + '_pro_clobbers.inc', gen, 'the ring prologue owns', [V_L0, V_LOFF, V_LANE], (), sgprs)
     return n, body
 
 
@@ -654,13 +555,8 @@ def emulate_tile(opts, img, aux, o, d, z, wave=0, n_tiles=1, check_hazards=True,
     for _ in range(n_tiles):
         st.xout = {}
         st.run(body)
-    errs = list(st.errors)
-    if st.pend_ds:
-        errs.append('%d LDS reads never waited for' % len(st.pend_ds))
-    if check_hazards:
-        errs += check_hazards_stream(body)
     out = np.stack([st.xout[i] for i in range(32)]).view(np.float32)
-    return out, errs
+    return out, isa.emulation_errors(st, [body] if check_hazards else [])
 
 
 def main():
@@ -679,11 +575,7 @@ def main():
         n, body = emit(a.emit, opts)
         print('wrote', a.emit, n, 'model cycles per tile', model_cycles(body))
     if a.dump:
-        body = block_stream(opts)
-        with open(a.dump, 'w') as f:
-            for ins in body:
-                f.write(ins.text + '\n')
-        print('model cycles per tile', model_cycles(body))
+        isa.dump_stream(a.dump, block_stream(opts), 'tile')
 
 
 if __name__ == '__main__':

@@ -1,9 +1,18 @@
 #!/usr/bin/env python3
-"""Instruction objects, number formats, the lane-accurate emulator state and the static hazard check shared by the gfx950
-stream generators (body_gen.py: R2L ResMLP body, 32x32 MFMA shapes; nerf_gen.py: NeRF teacher layer chain, 16x16 shapes).
+"""Instruction objects, number formats, the lane-accurate emulator state, the static hazard check and the scheduling machinery
+shared by the gfx950 stream generators (body_gen.py: R2L ResMLP body, 32x32 MFMA shapes; head_gen.py: R2L head layer, 32x32;
+nerf_gen.py: NeRF teacher layer chain, 16x16 shapes).
 
 Every instruction is an `Ins` with its assembly text, the registers it reads / writes and a Python closure that executes
 it on the emulator `State` (64 lanes x 256 VGPRs + 256 AGPRs, LDS bytes, in-order LDS-read and LDS-DMA queues).
+
+What places an instruction is here too, once, and holds no module state (a process may hold many generator instances):
+  * `Filler`, `ListSched`: the list scheduler -- chains, backward deadline propagation, and the phases of a generator's
+    anchor loop (start / due / fill / finish); a generator keeps its anchor loop, i.e. its MFMAs, waits and budgets;
+  * `Sched`: the stream being grown and the counted lgkmcnt waits (emit / need / landed);
+  * `lds_addr`, `dma_pieces`, `chunk_issue_seq`: ring addressing, the LDS-DMA piece loop, the fetch of a chunk;
+  * `write_inc`, `write_clobbers`, `kind_counts`, `counts_text`: the .inc files; `dump_stream`: --dump;
+  * `emulation_errors`: the end of every emulate_*; `OptsBase`: option sets that refuse a keyword they do not declare.
 
 Hazards a hand-written stream must respect by construction (hipcc pads nothing inside an asm statement);
 `check_hazards_stream` enforces them statically with a coarse cycle model:
@@ -749,6 +758,203 @@ class Filler:
         self.chain = chain        # fillers of one chain keep their order
         self.seq = 0
         self.needs = needs        # tags of LDS operations that must have completed (counted lgkmcnt in front of it)
+
+
+class Sched:
+    """the instruction list a schedule grows, with the bookkeeping of its counted lgkmcnt waits: LDS operations complete in
+    issue order, so "all but the youngest n have landed" is what one s_waitcnt can ask for"""
+
+    def __init__(self):
+        self.out = []             # the stream
+        self.its = []             # self.it at the time out[i] was emitted
+        self.it = None            # iteration of a software-pipelined loop being scheduled (body_gen), None elsewhere
+        self.ds_issued = 0        # LDS operations issued so far
+        self.ds_done = 0          # all LDS operations with index < ds_done are known complete
+        self.ds_index = {}        # tag -> index of its LDS operation
+
+    def emit(self, ins):
+        self.out.append(ins)
+        self.its.append(self.it)
+        if ins.kind == 'ds':
+            self.ds_index[ins.tag] = self.ds_issued
+            self.ds_issued += 1
+
+    def need(self, key, also=()):
+        """make sure the LDS read registered under `key` has landed; reads in `also` that have been issued by now ride along
+        (one s_waitcnt for a run of MFMAs: the instruction itself holds the wave's issue for some cycles, needed or not)"""
+        if key not in self.ds_index and self.it == 0:
+            return  # issued by the iteration before the schedule starts (iteration 0 is never the extracted one)
+        idx = self.ds_index[key]
+        if idx < self.ds_done:
+            return
+        for k2 in also:
+            if k2 in self.ds_index:
+                idx = max(idx, self.ds_index[k2])
+        n = min(15, self.ds_issued - idx - 1)         # the counter has 4 bits; waiting for more is always right
+        self.emit(waitcnt_lgkm(n))
+        self.ds_done = self.ds_issued - n
+
+    def landed(self):
+        """an s_waitcnt lgkmcnt(0) has just been emitted: nothing is in flight"""
+        self.ds_done = self.ds_issued
+
+
+class ListSched:
+    """list scheduler of the fillers around a fixed sequence of MFMA anchors.  The fillers are numbered in the order given
+    and grouped into chains; inside a chain a deadline is propagated backwards (a filler must not hold up a successor
+    with an earlier deadline).  A generator's anchor loop calls start(), then per anchor a: due(a), its own waits and
+    the MFMA through `sch`, fill(a, budget); finish() at the end.  Among the chain heads that may issue the earliest
+    deadline wins, then the lower number."""
+
+    def __init__(self, fillers, sch):
+        self.sch = sch
+        self.chains = {}
+        for i, f in enumerate(fillers):
+            f.seq = i
+            self.chains.setdefault(f.chain, []).append(f)
+        for ch in self.chains.values():
+            for i in range(len(ch) - 2, -1, -1):
+                ch[i].deadline = min(ch[i].deadline, ch[i + 1].deadline)
+        self.heads = {ch: 0 for ch in self.chains}
+
+    def ready(self, pos):
+        """chain heads that may issue once anchor `pos` has been emitted, by deadline"""
+        r = []
+        for ch, lst in self.chains.items():
+            i = self.heads[ch]
+            if i < len(lst) and lst[i].earliest <= pos:
+                r.append(lst[i])
+        r.sort(key=lambda f: (f.deadline, f.seq))
+        return r
+
+    def issue(self, f):
+        for key in f.needs:
+            self.sch.need(key)
+        self.sch.emit(f.ins)
+        self.heads[f.chain] += 1
+
+    def _drain(self, pos):
+        while True:
+            r = self.ready(pos)
+            if not r:
+                break
+            self.issue(r[0])
+
+    def start(self):
+        """everything that may issue in front of anchor 0 (position -1)"""
+        self._drain(-1)
+
+    def due(self, a):
+        """in front of anchor a: every filler whose deadline has come"""
+        while True:
+            r = [f for f in self.ready(a - 1) if f.deadline <= a]
+            if not r:
+                break
+            self.issue(r[0])
+
+    def fill(self, a, budget):
+        """behind anchor a: fillers while issue slots (Ins.cost) are left"""
+        while budget > 0:
+            r = self.ready(a)
+            if not r:
+                break
+            self.issue(r[0])
+            budget -= r[0].ins.cost
+
+    def finish(self):
+        """what is left, whatever its earliest anchor"""
+        self._drain(float('inf'))
+
+
+# ---------------------------------------------------------------------------------------------
+# pieces every generator needs around its schedule
+# ---------------------------------------------------------------------------------------------
+class OptsBase:
+    """options of a generator: a subclass sets every option and its default in declare(); a keyword that names none of them
+    is an error, not a new attribute"""
+
+    def __init__(self, **kw):
+        self.declare()
+        unknown = sorted(set(kw) - set(self.__dict__))
+        if unknown:
+            raise TypeError('%s has no option %s' % (type(self).__name__, ', '.join(unknown)))
+        self.__dict__.update(kw)
+
+
+def lds_addr(slot_bytes, bases, slot, byte_off, width):
+    """(base VGPR, immediate offset) of byte `byte_off` of ring slot `slot` for a per-lane width of 16 or 8 bytes;
+    bases = the VGPRs holding (lane*16, lane*16 + 65536, lane*8, lane*8 + 65536)"""
+    off = slot * slot_bytes + byte_off
+    lo, hi = bases[:2] if width == 16 else bases[2:]
+    return (lo, off) if off < 65536 else (hi, off - 65536)
+
+
+def dma_pieces(set_m0, pieces):
+    """a wave's LDS-DMA pieces of one chunk behind the M0 write `set_m0` (one instruction between an M0 write and an
+    LDS-DMA); pieces 4.. land 4 KiB further"""
+    seq = [set_m0, s_nop(0)]
+    for i, piece in enumerate(pieces):
+        if i == 4:
+            seq.append(salu('s_add_u32 m0, m0, 0x1000', lambda st: setattr(st, 'm0', st.m0 + 4096)))
+            seq.append(s_nop(0))
+        seq.append(piece)
+    return seq
+
+
+def chunk_issue_seq(s_g, s_w, s_wp, off, m0_off, pieces):
+    """SALU + LDS-DMA instructions that fetch a chunk at the immediate stream offset `off` into the ring at LDS byte
+    `m0_off`: source s[s_g:s_g+1] = s[s_w:s_w+1] + s[s_wp] + off, M0 = s[s_wp] + m0_off (s_wp: this wave's share)"""
+    seq = [salu('s_add_u32 %s, %s, %s' % (sreg(s_g), sreg(s_w), sreg(s_wp)), lambda st: st.S.__setitem__(s_g, st.S[s_w] + st.S[s_wp])),
+           salu('s_addc_u32 %s, %s, 0' % (sreg(s_g + 1), sreg(s_w + 1)))]
+    if off:
+        seq += [salu('s_add_u32 %s, %s, 0x%x' % (sreg(s_g), sreg(s_g), off), lambda st: st.S.__setitem__(s_g, st.S[s_g] + off)),
+                salu('s_addc_u32 %s, %s, 0' % (sreg(s_g + 1), sreg(s_g + 1)))]
+    set_m0 = salu('s_add_u32 m0, %s, 0x%x' % (sreg(s_wp), m0_off), lambda st: setattr(st, 'm0', st.S[s_wp] + m0_off))
+    return seq + dma_pieces(set_m0, pieces)
+
+
+def kind_counts(body):
+    n = {}
+    for ins in body:
+        n[ins.kind] = n.get(ins.kind, 0) + 1
+    return n
+
+
+def counts_text(n):
+    return ', '.join('%s %d' % kv for kv in sorted(n.items()))
+
+
+def write_inc(path, gen, what, lines):
+    """an inline-asm include file: a header comment, then one quoted line per instruction"""
+    with open(path, 'w') as f:
+        f.write('// GENERATED by gen/%s -- do not edit.  %s\n' % (gen, what))
+        for line in lines:
+            f.write('"%s\\n\\t"\n' % line)
+
+
+def write_clobbers(path, gen, what, vregs, aregs, sregs):
+    """the clobber list of an asm statement that owns VGPRs `vregs`, AGPRs `aregs` and SGPRs `sregs` (iterables of numbers)"""
+    regs = ['v%d' % i for i in vregs] + ['a%d' % i for i in aregs] + ['s%d' % i for i in sregs] + ['vcc', 'scc', 'memory']
+    with open(path, 'w') as f:
+        f.write('// GENERATED by gen/%s: registers %s\n' % (gen, what) + ', '.join('"%s"' % r for r in regs) + '\n')
+
+
+def emulation_errors(st, streams):
+    """what an emulation ends with: the errors the state collected, LDS reads still in flight, the static hazard check of `streams`"""
+    errs = list(st.errors)
+    if st.pend_ds:
+        errs.append('%d LDS reads never waited for' % len(st.pend_ds))
+    for stream in streams:
+        errs += check_hazards_stream(stream)
+    return errs
+
+
+def dump_stream(path, body, unit):
+    """--dump: the stream as plain text, and its length in the coarse issue model"""
+    with open(path, 'w') as f:
+        for ins in body:
+            f.write(ins.text + '\n')
+    print('model cycles per %s' % unit, model_cycles(body))
 
 
 

@@ -41,7 +41,7 @@ import numpy as np
 import isa as B
 from isa import (Ins, vr, ar, vreg, areg, sreg, waitcnt_lgkm, waitcnt_vm, barrier, valu, v_max0, v_accw, v_accr, v_cvt_pk_f16,
                  v_cvt_pk32_bf6, s_nop, salu, ds_read_b128, ds_read_b64, f_to_bf6, pack6, layer_exponent, weight_exps,
-                 f32_bits, Filler, check_hazards_stream, kappa16 as kappa, mix16 as mix_feat)
+                 f32_bits, Filler, Sched, ListSched, OptsBase, model_cycles, kappa16 as kappa, mix16 as mix_feat)
 
 # ---------------------------------------------------------------------------------------------
 # the variants of the chain: the ONLY place this generator names them (NERF_GEN_FMT selects a row; the comments at FMT below say what
@@ -195,6 +195,7 @@ else:
 # mix: AGPRs above the bf6 sets (0..95) that the block owns besides them: the last 16 registers of lo(Q) and of lo(P) (lset).  The
 # compiler keeps the 48 input registers and what it carries across the block (the next tile's rays) out of both.
 A_EXTRA_CLOBBER = (224, 256) if MIX else None
+L_BASES = (V_L0, V_L1, V_L8A, V_L8B)
 if EMB:
     V_OUT = N_VGPR_CLOBBER        # 16: (rgb, sigma) of the four column tiles -- and the embedding's temporaries until the RGB epilogue
     V_SIG = V_OUT + 16            # 4: sigma of the column tiles (FA's last row tile), moved into V_OUT at the tail
@@ -1225,8 +1226,8 @@ def vm_wait(n):
 
 
 
-class Opts:
-    def __init__(self, **kw):
+class Opts(OptsBase):
+    def declare(self):
         self.lead = 8          # anchors a fragment read is issued ahead of its first MFMA
         self.lead6 = 5
         self.cap = 3           # issue slots for fillers behind each MFMA
@@ -1240,13 +1241,8 @@ class Opts:
         if NC > 2:             # three (four) MFMAs per fragment: fewer filler slots behind each, LDS-DMA pieces further apart (same-box sweep:
             self.cap = 2       # cap 2 / 3 / 4 / 5 = 36.9 / 37.2 / 37.3 / 37.6 ms per frame, gap 3 / 4 / 6 = 37.5 / 37.2 / 36.9, both: -1.4 %)
             self.dma_gap = 2 * NC          # (four column tiles: gap 4 / 6 / 8 = 34.75 / 34.35 / 34.2 ms)
-        self.__dict__.update(kw)
-
-
-def lds_addr(slot, byte_off, width):
-    off = slot * SLOT + byte_off
-    lo, hi = (V_L0, V_L1) if width == 16 else (V_L8A, V_L8B)
-    return (lo, off) if off < 65536 else (hi, off - 65536)
+        self.drop = ()         # diagnostics only (wrong results): instruction classes left out of the emitted text (--drop)
+        self.a_emb = None      # f16c4e: set by build_fillers, the anchor from which the embedding fillers may run
 
 
 def rdv_anchor(ci):
@@ -1257,25 +1253,11 @@ def rdv_anchor(ci):
     return afirst(ts[0]) + len(ANCH[ts[0]]) // 2
 
 
-def chunk_issue_seq(cn, slot):
-    """SALU + LDS-DMA instructions that fetch chunk cn (index into the tile's stream, wrapped) into ring slot `slot`"""
-    ch = CHUNKS[cn % NCH]
-    pw = ch['pw']
-    off = CHUNK_OFF[cn % NCH]
-    wp = S_WPW + pw - 1
-    seq = [salu('s_add_u32 %s, %s, %s' % (sreg(S_G), sreg(S_W), sreg(wp)), lambda st: st.S.__setitem__(S_G, st.S[S_W] + st.S[wp])),
-           salu('s_addc_u32 %s, %s, 0' % (sreg(S_G + 1), sreg(S_W + 1)))]
-    if off:
-        seq += [salu('s_add_u32 %s, %s, 0x%x' % (sreg(S_G), sreg(S_G), off), lambda st: st.S.__setitem__(S_G, st.S[S_G] + off)),
-                salu('s_addc_u32 %s, %s, 0' % (sreg(S_G + 1), sreg(S_G + 1)))]
-    seq.append(salu('s_add_u32 m0, %s, 0x%x' % (sreg(wp), slot * SLOT), lambda st: setattr(st, 'm0', st.S[wp] + slot * SLOT)))
-    seq.append(s_nop(0))
-    for i in range(pw):
-        if i == 4:
-            seq.append(salu('s_add_u32 m0, m0, 0x1000', lambda st: setattr(st, 'm0', st.m0 + 4096)))
-            seq.append(s_nop(0))
-        seq.append(dma_piece(i, pw, tag=('dma', cn, i)))
-    return seq, pw
+def fetch_chunk(cn, slot):
+    """(SALU + LDS-DMA instructions that fetch chunk cn (index into the tile's stream, wrapped) into ring slot `slot`, pieces per wave)"""
+    pw = CHUNKS[cn % NCH]['pw']
+    return B.chunk_issue_seq(S_G, S_W, S_WPW + pw - 1, CHUNK_OFF[cn % NCH], slot * SLOT,
+                             [dma_piece(i, pw, tag=('dma', cn, i)) for i in range(pw)]), pw
 
 
 def build_fillers(opts):
@@ -1304,7 +1286,7 @@ def build_fillers(opts):
         L = TILES[T].layer
         ci, kc = TILE_CHUNK[T]
         pc, po = piece_of(L, kc, what, k)
-        bv, off = lds_addr(ci % NSLOT, pc * 1024 + po, 16)
+        bv, off = B.lds_addr(SLOT, L_BASES, ci % NSLOT, pc * 1024 + po, 16)
         buf = V_HI + (n % N_FRAG_BUF) * 4
         bufmap[key] = buf
         hard = last[hi_keys[n - N_FRAG_BUF]] if n >= N_FRAG_BUF else -1
@@ -1318,10 +1300,10 @@ def build_fillers(opts):
         hard = last[a6_keys[n - 2]] if n >= 2 else -1
         e = max(hard, first[key] - opts.lead6, certified(T))
         pc, po = piece_of(L, kc, 'b6', k)
-        bv, off = lds_addr(ci % NSLOT, pc * 1024 + po, 16)
+        bv, off = B.lds_addr(SLOT, L_BASES, ci % NSLOT, pc * 1024 + po, 16)
         F.append(Filler(ds_read_b128(buf, bv, off, tag=key + (0,)), e, first[key], ('rd6',)))
         pc, po = piece_of(L, kc, 'b6b', k)
-        bv, off = lds_addr(ci % NSLOT, pc * 1024 + po, 8)
+        bv, off = B.lds_addr(SLOT, L_BASES, ci % NSLOT, pc * 1024 + po, 8)
         F.append(Filler(ds_read_b64(buf + 4, bv, off, tag=key + (1,)), e, first[key], ('rd6',)))
     # ---- bias and scales (resident table) ------------------------------------------------------------
     for T, t in enumerate(TILES):
@@ -1369,7 +1351,7 @@ def build_fillers(opts):
         ch = ('dma',)
         F.append(Filler((vm_wait if EMB else waitcnt_vm)(group.get(ci + 2, 0)), ar - 1, ar + 1, ch))
         F.append(Filler(barrier(), ar - 1, ar + 1, ch))
-        seq, pw = chunk_issue_seq(ci + 3, (ci + 3) % NSLOT)
+        seq, pw = fetch_chunk(ci + 3, (ci + 3) % NSLOT)
         group[ci + 3] = pw
         k = 0
         for ins in seq:
@@ -1456,72 +1438,16 @@ def skip_tail_ops():
     return ops
 
 
-class Sched:
-    def __init__(self):
-        self.out = []
-        self.ds_issued = 0
-        self.ds_done = 0
-        self.ds_index = {}
-
-    def emit(self, ins):
-        self.out.append(ins)
-        if ins.kind == 'ds':
-            self.ds_index[ins.tag] = self.ds_issued
-            self.ds_issued += 1
-
-    def need(self, key, also=()):
-        """wait for the LDS read `key`; reads in `also` that have been issued ride along (one s_waitcnt for a run of MFMAs)"""
-        idx = self.ds_index[key]
-        if idx < self.ds_done:
-            return
-        for k2 in also:
-            if k2 in self.ds_index:
-                idx = max(idx, self.ds_index[k2])
-        n = min(15, self.ds_issued - idx - 1)
-        self.emit(waitcnt_lgkm(n))
-        self.ds_done = self.ds_issued - n
-
-
 def schedule(opts):
     """the tile block between its entry (vmcnt(0) + barrier) and its exposed last epilogue: [Ins]"""
     sch = Sched()
     fillers, bufmap = build_fillers(opts)
-    for i, f in enumerate(fillers):
-        f.seq = i
-    chains = {}
-    for f in fillers:
-        chains.setdefault(f.chain, []).append(f)
-    for ch in chains.values():
-        for i in range(len(ch) - 2, -1, -1):   # a filler must not hold up a successor with an earlier deadline
-            ch[i].deadline = min(ch[i].deadline, ch[i + 1].deadline)
-    heads = {ch: 0 for ch in chains}
-
-    def ready(pos):
-        r = []
-        for ch, lst in chains.items():
-            i = heads[ch]
-            if i < len(lst) and lst[i].earliest <= pos:
-                r.append(lst[i])
-        r.sort(key=lambda f: (f.deadline, f.seq))
-        return r
-
-    def issue(f):
-        sch.emit(f.ins)
-        heads[f.chain] += 1
-
-    while True:
-        r = ready(-1)
-        if not r:
-            break
-        issue(r[0])
+    ls = ListSched(fillers, sch)
+    ls.start()
     T = 0
     a_cut = afirst(TILE_OF[([l.name for l in CHAIN].index('F'), 0)]) if SKIPV else -1
     for a in range(N_ANCH):
-        while True:
-            r = [f for f in ready(a - 1) if f.deadline <= a]
-            if not r:
-                break
-            issue(r[0])
+        ls.due(a)
         while a >= ABASE[T + 1]:
             T += 1
         if a == a_cut:          # the second exit sits between layer A's last MFMA and layer F's first
@@ -1531,7 +1457,7 @@ def schedule(opts):
                 else:
                     sch.emit(ins)
                     if ins.kind == 'wait' and 'lgkmcnt(0)' in ins.text:
-                        sch.ds_done = sch.ds_issued
+                        sch.landed()
         t = TILES[T]
         L = t.layer
         kind, k, c, p = ANCH[T][a - ABASE[T]]
@@ -1565,17 +1491,8 @@ def schedule(opts):
         budget = opts.cap if not opts.pair else (0 if c == 0 else 2 * opts.cap)   # pair: fillers only behind the c = 1 MFMA
         if EMB and a >= opts.a_emb:
             budget = opts.cap_late
-        while budget > 0:
-            r = ready(a)
-            if not r:
-                break
-            issue(r[0])
-            budget -= r[0].ins.cost
-    while True:          # what is left of the refill of the next tile's first chunks
-        r = ready(N_ANCH + 10 ** 6)
-        if not r:
-            break
-        issue(r[0])
+        ls.fill(a, budget)
+    ls.finish()          # what is left of the refill of the next tile's first chunks
     return sch.out
 
 
@@ -1630,7 +1547,7 @@ def prologue_ops():
     """ring prologue: chunks 0, 1, 2 -> slots 0, 1, 2"""
     seq = []
     for k in range(3):
-        seq += chunk_issue_seq(k, k)[0]
+        seq += fetch_chunk(k, k)[0]
     return seq
 
 
@@ -1749,19 +1666,12 @@ def kernel_text(opts):
 
 def emit_kernel(dirname, opts):
     lines, body = kernel_text(opts)
-    n = {}
-    for ins in body:
-        n[ins.kind] = n.get(ins.kind, 0) + 1
+    n = B.kind_counts(body)
     f_asm, f_clob = [os.path.join(dirname, x) for x in inc_files(VARIANT)]
-    with open(f_asm, 'w') as f:
-        f.write('// GENERATED by gen/nerf_gen.py (NERF_GEN_FMT=%s) -- do not edit.  The fp16-only teacher chain as one statement: ring prologue, first '
-                "tile's embedding, tile loop (ray loads, eleven layers, the next tile's embedding as fillers, raw stores).  Per tile: %s\n" %
-                (VARIANT, ', '.join('%s %d' % kv for kv in sorted(n.items()))))
-        for line in lines:
-            f.write('"%s\\n\\t"\n' % line)
-    regs = ['v%d' % i for i in range(256)] + ['a%d' % i for i in range(256)] + ['s%d' % i for i in range(N_SGPR_LO, N_SGPR_HI)] + ['vcc', 'scc', 'memory']
-    with open(f_clob, 'w') as f:
-        f.write('// GENERATED by gen/nerf_gen.py: registers the kernel statement owns\n' + ', '.join('"%s"' % r for r in regs) + '\n')
+    B.write_inc(f_asm, 'nerf_gen.py (NERF_GEN_FMT=%s)' % VARIANT, 'The fp16-only teacher chain as one statement: ring prologue, first '
+                "tile's embedding, tile loop (ray loads, eleven layers, the next tile's embedding as fillers, raw stores).  Per tile: " +
+                B.counts_text(n), lines)
+    B.write_clobbers(f_clob, 'nerf_gen.py', 'the kernel statement owns', range(256), range(256), range(N_SGPR_LO, N_SGPR_HI))
     return n, body
 
 
@@ -1776,7 +1686,6 @@ def emulate_kernel(opts, img, aux, rays_o, rays_d, z, S, z_stride, n_pts, wave=0
     setup(st, dict(npts=n_pts, S=S, zs=z_stride, magic=magic, sh1=sh1, sh2=sh2, tile=block, grid=grid, ntiles=n_tiles))
     st.gmem = {'rays_o': np.ascontiguousarray(rays_o, dtype=np.float32).reshape(-1), 'rays_d': np.ascontiguousarray(rays_d, dtype=np.float32).reshape(-1),
                'z': np.ascontiguousarray(z, dtype=np.float32).reshape(-1), 'raw': np.full(n_pts * 4, np.nan, dtype=np.float32)}
-    errs = []
     if block < n_tiles:
         st.run(prologue_ops())
         st.S[S_NEXT] = st.S[S_TILE]
@@ -1790,53 +1699,31 @@ def emulate_kernel(opts, img, aux, rays_o, rays_d, z, S, z_stride, n_pts, wave=0
             st.S[S_NEXT] = st.S[S_NEXT] + st.S[S_GRID]
             if not st.S[S_TILE] < st.S[S_NTILES]:
                 break
-    errs += list(st.errors)
-    if st.pend_ds:
-        errs.append('%d LDS reads never waited for' % len(st.pend_ds))
-    if check_hazards:
-        errs += check_hazards_stream(body)
-        errs += check_hazards_stream(first_embed_ops())
-    return st.gmem['raw'].reshape(n_pts, 4), errs
+    return st.gmem['raw'].reshape(n_pts, 4), B.emulation_errors(st, [body, first_embed_ops()] if check_hazards else [])
 
 
 
 def emit(dirname, opts):
     setup, _ = setup_ops()
     body = block_stream(opts)
-    drop = getattr(opts, 'drop', ())          # diagnostics only (wrong results): timing knock-outs of instruction classes
+    drop = opts.drop
     if drop:
         def keep(i):
             if i.kind == 'wait':
                 return not (('lgkm' in drop and 'lgkmcnt' in i.text) or ('vm' in drop and 'vmcnt' in i.text))
             return i.kind not in drop
         body = [i for i in body if keep(i)]
-    n = {}
-    for ins in body:
-        n[ins.kind] = n.get(ins.kind, 0) + 1
+    n = B.kind_counts(body)
     f_asm, f_pro, f_clob, f_pro_clob = [os.path.join(dirname, x) for x in inc_files(VARIANT)]
-    with open(f_asm, 'w') as f:
-        f.write('// GENERATED by gen/nerf_gen.py -- do not edit.  One 128-point tile of the teacher MLP: %s\n' %
-                ', '.join('%s %d' % kv for kv in sorted(n.items())))
-        lines = setup + [i.text for i in body]
-        if SKIPV:
-            lines += ['s_branch L_done_%=', 'L_skip_%=:'] + [i.text for i in skip_tail_ops()] + ['L_done_%=:']
-        for line in lines + ['s_mov_b32 m0, %s' % sreg(S_M0SAVE)]:
-            f.write('"%s\\n\\t"\n' % line)
-    with open(f_pro, 'w') as f:
-        f.write('// GENERATED by gen/nerf_gen.py -- do not edit.  Ring prologue: chunks 0..2 of the stream\n')
-        for line in setup + [i.text for i in prologue_ops()] + ['s_mov_b32 m0, %s' % sreg(S_M0SAVE)]:
-            f.write('"%s\\n\\t"\n' % line)
-    def clob(nv0, nv1, na):
-        regs = ['v%d' % i for i in range(nv0, nv1)] + ['a%d' % i for i in range(na)]
-        if na and A_EXTRA_CLOBBER:
-            regs += ['a%d' % i for i in range(*A_EXTRA_CLOBBER)]
-        regs += ['s%d' % i for i in range(N_SGPR_LO, N_SGPR_HI)] + ['vcc', 'scc', 'memory']
-        return ', '.join('"%s"' % r for r in regs) + '\n'
-
-    with open(f_clob, 'w') as f:
-        f.write('// GENERATED by gen/nerf_gen.py: registers the tile block owns\n' + clob(0, N_VGPR_CLOBBER, N_AGPR_CLOBBER))
-    with open(f_pro_clob, 'w') as f:
-        f.write('// GENERATED by gen/nerf_gen.py: registers the ring prologue owns\n' + clob(V_L0, N_VGPR_CLOBBER, 0))
+    gen, sgprs, restore = 'nerf_gen.py', range(N_SGPR_LO, N_SGPR_HI), ['s_mov_b32 m0, %s' % sreg(S_M0SAVE)]
+    lines = setup + [i.text for i in body]
+    if SKIPV:
+        lines += ['s_branch L_done_%=', 'L_skip_%=:'] + [i.text for i in skip_tail_ops()] + ['L_done_%=:']
+    B.write_inc(f_asm, gen, 'One 128-point tile of the teacher MLP: ' + B.counts_text(n), lines + restore)
+    B.write_inc(f_pro, gen, 'Ring prologue: chunks 0..2 of the stream', setup + [i.text for i in prologue_ops()] + restore)
+    aregs = list(range(N_AGPR_CLOBBER)) + (list(range(*A_EXTRA_CLOBBER)) if A_EXTRA_CLOBBER else [])
+    B.write_clobbers(f_clob, gen, 'the tile block owns', range(N_VGPR_CLOBBER), aregs, sgprs)
+    B.write_clobbers(f_pro_clob, gen, 'the ring prologue owns', range(V_L0, N_VGPR_CLOBBER), (), sgprs)
     return n, body
 
 
@@ -1862,21 +1749,12 @@ def emulate_tile(opts, img, aux, frags, wave=0, n_tiles=1, check_hazards=True, b
             st.run(skip_tail_ops() if st.skip else post)
         else:
             st.run(body)
-    errs = list(st.errors)
-    if st.pend_ds:
-        errs.append('%d LDS reads never waited for' % len(st.pend_ds))
-    if check_hazards:
-        errs += check_hazards_stream(body)
-        if SKIPV:
-            errs += check_hazards_stream(split_at_cut(body)[0] + skip_tail_ops())
+    streams = [body] + ([split_at_cut(body)[0] + skip_tail_ops()] if SKIPV else [])       # both exits
+    errs = B.emulation_errors(st, streams if check_hazards else [])
     out = np.stack([st.out[k] for k in range(4 * NC)]).view(np.float32)
     if SKIPV:
         return out, errs, st.skipped
     return out, errs
-
-
-def model_cycles(body):
-    return B.model_cycles(body)
 
 
 def main():
@@ -1899,11 +1777,7 @@ def main():
         n, body = (emit_kernel if EMB else emit)(a.emit, opts)
         print('wrote', a.emit, n, 'model cycles per tile', model_cycles(body))
     if a.dump:
-        body = block_stream(opts)
-        with open(a.dump, 'w') as f:
-            for ins in body:
-                f.write(ins.text + '\n')
-        print('model cycles per tile', model_cycles(body))
+        B.dump_stream(a.dump, block_stream(opts), 'tile')
 
 
 if __name__ == '__main__':
