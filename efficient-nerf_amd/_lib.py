@@ -142,6 +142,12 @@ SIGNATURES = {
     'r2l_lpips_workspace_floats': (C.c_longlong, [C.c_int, C.c_int]),
     'r2l_lpips': (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                             _vp, _vp, _vp, C.c_longlong, _vp]),
+    # Motion-JPEG (csrc/r2l_mjpeg.hip)
+    'r2l_mjpeg_tables': (C.c_int, [C.c_int, _vp, _vp]),
+    'r2l_mjpeg_header': (C.c_longlong, [C.c_int, C.c_int, C.c_int, _vp, C.c_longlong]),
+    'r2l_mjpeg_workspace_bytes': (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
+    'r2l_mjpeg_max_frame_bytes': (C.c_longlong, [C.c_int, C.c_int]),
+    'r2l_mjpeg_encode': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_longlong, _vp, C.c_longlong, _vp, _vp, _vp]),
     # teacher training (csrc/nerf_train.hip)
     'nerf_train_raw2outputs_backward': (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     'nerf_train_batch_rays': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_longlong, C.c_int, C.c_float, _vp, _vp, _vp,

@@ -98,6 +98,9 @@ FLAGS = [
     ('--i_testset', dict(type=int, default=2000)), ('--i_video', dict(type=int, default=10000)),
     ('--select_pixel_mode', dict(type=str, default='rand_pixel', choices=['rand_pixel', 'rand_patch'])),
     # this front-end's own knobs
+    # the fly-through video (main.py:1096-1098, :1474-1499) as Motion-JPEG in an AVI file, encoded on the device (video.py, csrc/r2l_mjpeg.hip):
+    # --render_only writes <outdir>/video[_<video_tag>].avi, training video_iter<i>[_<video_tag>].avi every --i_video iterations; off by default
+    ('--write_video', dict(action=_BOOL)), ('--video_quality', dict(type=int, default=90)), ('--video_fps', dict(type=float, default=30)),
     # auto (default): fp16_fp8 (fp16 MFMA pass + bf6 correction terms, 1.7x the speed) when the checkpoint's own activation
     # ranges, measured on every ray of the first frame and watched on every frame after it, keep it inside the 1e-4 rgb
     # contract, fp16x3_asm otherwise (R2LEngine.choose_precision / check_ranges); the teacher measures fp16x1 (its layer chain as one
@@ -828,6 +831,8 @@ def main(argv=None):
     args = parse_args(argv)
     from .metrics import LPIPS, lpips_weights_from_args
     args.lpips_tensors = lpips_weights_from_args(args)        # --test_lpips: refused here, before a device is touched, or loaded once
+    from .video import check_video_args, video_path, write_video
+    check_video_args(args)
     if not args.render_only:
         if args.model_name not in ('R2L', 'nerf_v3.2'):
             raise SystemExit(f'--model_name {args.model_name} without --render_only: teacher training is not built (the student trains: '
@@ -933,4 +938,12 @@ def main(argv=None):
                 f"TestSSIM {misc['test_ssim']:.4f}" + (f" TestLPIPS {misc['test_lpips']:.4f}" if 'test_lpips' in misc else '') +
                 (f" TestFLIP {misc['test_flip']:.4f}" if 'test_flip' in misc else ''))
         log(f'Save renders: "{outdir}"')
+        if args.write_video:                  # main.py:1096-1098: the stack rank 0 holds, encoded where it lies
+            t_ = time.time()
+            path = video_path(outdir, args)
+            try:
+                n, size = write_video(path, rgbs if rgbs.is_cuda else rgbs.cuda(), fps=args.video_fps, quality=args.video_quality)
+            except ValueError as e:
+                raise SystemExit(str(e))
+            log(f'Save video: "{path}" ({n} frames, {size / 1e6:.2f} MB, time: {time.time() - t_:.2f}s)')
     return 0

@@ -397,7 +397,7 @@ def refuse_negative_i_testset(args):
 
 
 def run_iterations(args, trainer, start, best, weights_dir, log, *, draw, after_step, test_pass=None,
-                   ckpt_name=lambda it: 'ckpt.tar', step_args={}, writer=True, guard=None):
+                   ckpt_name=lambda it: 'ckpt.tar', step_args={}, writer=True, guard=None, video_pass=None):
     """Iterations start + 1 .. N_iters of main.py:1136-1513 on either trainer: the learning rate, the step, the [TRAIN] line, the
     test renders every --i_testset iterations (0: none) with the best checkpoint and the [TEST] line, the periodic and the final
     checkpoint.  Returns the path of the last checkpoint written.  What differs between the trainers comes in as
@@ -405,11 +405,12 @@ def run_iterations(args, trainer, start, best, weights_dir, log, *, draw, after_
       after_step(batch, second) -> the mse the line's psnr is of, or None for the loss; second: what trainer.step returned second
       test_pass(i)              -> (test_psnr, test_psnr_v2, further fields of the [TEST] line, a line to log after it or None)
       ckpt_name(i)              -> the periodic checkpoint's file name
+      video_pass(i)             -> renders and writes the video of iteration i (every --i_video iterations, 0: never; --write_video)
     best: (best_psnr, best_psnr_step) so far; step_args: passed on to trainer.step beside perturb.
     On the ranks of a ray-sharded run every rank runs this loop on the same batches: writer is True on the one rank that renders the
     test split and writes files (the others go on to the next step's collective), and guard(i) is entered by every rank before
-    anything is written at iteration i (it raises on every rank when their weights differ); test_pass is then given on every rank
-    or on none."""
+    anything is written at iteration i (it raises on every rank when their weights differ); test_pass, and likewise video_pass, is
+    then given on every rank or on none."""
     from .frontend import mse2psnr
     best_psnr, best_psnr_step = best
     save = lambda name, it: save_train_checkpoint(os.path.join(weights_dir, name), trainer, it, best_psnr, best_psnr_step)
@@ -454,6 +455,11 @@ def run_iterations(args, trainer, start, best, weights_dir, log, *, draw, after_
                 f'{fields}TrainHistPSNR {hist_psnr:.4f} LR {lr:.8f} Time {t_test:.1f}s')
             if after:
                 log(after)
+        videoing = video_pass is not None and args.i_video and i % args.i_video == 0      # main.py:1474-1499
+        if videoing:
+            agree(i)
+        if videoing and writer:
+            video_pass(i)
         if i % args.i_weights == 0:
             agree(i)
             if writer:
@@ -675,6 +681,17 @@ def _train(args, log, engines):
         flip_field = (f"TestLPIPS {misc['test_lpips']:.4f} " if lpips is not None else '') + (f"TestFLIP {misc['test_flip']:.4f} " if flip_on else '')
         return misc['test_psnr'], misc['test_psnr_v2'], f"TestSSIM {misc['test_ssim']:.4f} " + flip_field, f'Saved rendered test images: "{testsavedir}"'
 
+    video_pass = None
+    if getattr(args, 'write_video', False):   # on every rank: the others enter the agreement guard where rank 0 renders
+        from . import video as V
+        V.check_video_args(args)
+        if rank == 0:
+            v_poses, v_hwf = V.training_video_poses(args, hwf=test[1] if test is not None else None)
+            video_pass = lambda i: V.video_pass(i, args, expdir, log, v_poses, v_hwf,
+                                                lambda pose, out: trainer.render(pose, *v_hwf, out=out))
+        else:
+            video_pass = lambda i: None
+
     stepper, guard = trainer, None
     if world > 1:
         stepper = ShardedStep(trainer)
@@ -682,4 +699,4 @@ def _train(args, log, engines):
     return run_iterations(args, stepper, start, (best_psnr, best_psnr_step), weights_dir, log, draw=draw, after_step=after_step,
                           test_pass=test_pass if has_test else None,
                           ckpt_name=lambda it: f'ckpt_{it}.tar' if args.save_intermediate_models else 'ckpt.tar',      # main.py:1510
-                          writer=rank == 0, guard=guard)
+                          writer=rank == 0, guard=guard, video_pass=video_pass)

@@ -480,7 +480,7 @@ REFUSALS = {
     'llff_no_batching': '--dataset_type llff: teacher training is built for Blender scenes with no_batching; LLFF scenes train with '
                         'use_batching (no --no_batching / no_batching line, as configs/fern.txt)',
     'rand_patch': '--select_pixel_mode rand_patch: teacher training selects pixels with rand_pixel',
-    'i_video': '--i_video {} falls inside this run: the video render is not built for training; pass an --i_video above --N_iters',
+    'i_video': '--i_video {} falls inside this run: the video render is not built for training; pass an --i_video above --N_iters',      # lifted by --write_video
     'datadir_kd': '--datadir_kd with --data_mode images: pseudo images are not built for teacher training',
     'data_mode': '--data_mode {}: the teacher trains on images (--data_mode images)',
     'model_name': '--model_name {}: train_teacher.py trains --model_name nerf (main.py trains the student)',
@@ -504,7 +504,7 @@ def check_supported(args, start=0):
         raise SystemExit(REFUSALS['data_mode'].format(args.data_mode))
     if args.datadir_kd:
         raise SystemExit(REFUSALS['datadir_kd'])
-    if args.i_video > 0 and args.N_iters // args.i_video > start // args.i_video:
+    if not getattr(args, 'write_video', False) and args.i_video > 0 and args.N_iters // args.i_video > start // args.i_video:
         raise SystemExit(REFUSALS['i_video'].format(args.i_video))
     refuse_negative_i_testset(args)
 
@@ -517,9 +517,8 @@ def trainer_from_args(args, max_rays, near=2., far=6.):
                        white_bkgd=args.white_bkgd, lindisp=args.lindisp, max_rays=max_rays)
 
 
-def eval_test_split(trainer, args, hwf, poses, gt, near=2., far=6., ndc=False):
-    """render_path over the test split from the current weights (main.py:1442-1456) on generic.GenericNeRF: (test_psnr, test_psnr_v2)"""
-    from .frontend import mse2psnr
+def test_engine(trainer, args, hwf, near=2., far=6., ndc=False):
+    """generic.GenericNeRF at hwf with the trainer's current weights: what the test split and the video are rendered on"""
     from .generic import GenericNeRF
     H, W, focal = hwf
     eng = GenericNeRF(H, W, focal, near, far, N_samples=args.N_samples, N_importance=args.N_importance, multires=args.multires,
@@ -527,6 +526,14 @@ def eval_test_split(trainer, args, hwf, poses, gt, near=2., far=6., ndc=False):
                       netdepth_fine=args.netdepth_fine, netwidth_fine=args.netwidth_fine, use_viewdirs=args.use_viewdirs,
                       white_bkgd=args.white_bkgd, lindisp=args.lindisp, ndc=ndc, device=trainer.device)
     eng.load_state_dicts(*trainer.state_dicts())
+    return eng
+
+
+def eval_test_split(trainer, args, hwf, poses, gt, near=2., far=6., ndc=False):
+    """render_path over the test split from the current weights (main.py:1442-1456) on generic.GenericNeRF: (test_psnr, test_psnr_v2)"""
+    from .frontend import mse2psnr
+    H, W, focal = hwf
+    eng = test_engine(trainer, args, hwf, near, far, ndc)
     mses = []
     for pose, img in zip(poses, gt):
         rgb = eng.render(pose[:3, :4])['rgb_map'].view(H, W, 3)
@@ -631,11 +638,23 @@ def train(args, log=print):
         test_psnr, test_psnr_v2 = eval_test_split(trainer, args, data['hwf'], *data['test'], near=near, far=far, ndc=data['ndc'])
         return test_psnr, test_psnr_v2, '', None
 
+    video_pass = None
+    if getattr(args, 'write_video', False):   # main.py:1474-1499, the rgb video; the disparity video is not built
+        from . import video as V
+        V.check_video_args(args)
+        v_poses, v_hwf = V.training_video_poses(args, hwf=data['hwf'])
+        expdir = os.path.dirname(weights_dir)
+
+        def video_pass(i):
+            eng = test_engine(trainer, args, v_hwf, near, far, data['ndc'])
+            return V.video_pass(i, args, expdir, log, v_poses, v_hwf, lambda pose, out: out.copy_(eng.render(pose[:3, :4])['rgb_map'].view(-1, 3)))
+
     step_args = data['step_args']
     step_args['raw_noise_std'] = args.raw_noise_std
     # the [TRAIN] line's psnr is of img2mse(rgb) alone (main.py:1377-1379)
     return run_iterations(args, trainer, start, (best_psnr, best_psnr_step), weights_dir, log, draw=data['draw'],
-                          after_step=lambda batch, loss_rgb: float(loss_rgb.item()), test_pass=test_pass, step_args=step_args)
+                          after_step=lambda batch, loss_rgb: float(loss_rgb.item()), test_pass=test_pass, step_args=step_args,
+                          video_pass=video_pass)
 
 
 def main(argv=None):

@@ -594,6 +594,31 @@ long long r2l_lpips_workspace_floats(int H, int W);
 int r2l_lpips(const r2l_lpips_ctx* l, const float* a_dev, const float* b_dev, int n_img, int H, int W, float a_lo, float a_mul, float a_add, float b_lo,
               float b_mul, float b_add, float* d_dev, float* layers_dev, float* workspace_dev, long long workspace_floats, void* stream);
 
+/* ---- Motion-JPEG frames (csrc/r2l_mjpeg.hip; host side: efficient-nerf_amd/video.py) ----
+ * Each frame of rgb_dev, float32 [n_img, H, W, 3], becomes one complete baseline JPEG file (ITU-T T.81: sequential DCT, 8 bit, Huffman):
+ * Y, Cb, Cr in the JFIF colour space, 4:4:4 (every sampling factor 1), one interleaved scan, no restart markers.  A pixel is
+ * p = floor(255 clamp(x, 0, 1)), the front end's to8b, with NaN = 0; H and W are padded up to multiples of 8 by repeating the last row
+ * and column; Y = 0.299 R + 0.587 G + 0.114 B - 128, Cb = -0.168736 R - 0.331264 G + 0.5 B, Cr = 0.5 R - 0.418688 G - 0.081312 B and the
+ * FDCT of T.81 A.3.3 in fp32; coefficients are divided by the quantiser and rounded to nearest, AC clamped to +-1023.  The quantisers
+ * are Annex K.1 / K.2 scaled by libjpeg's rule (s = 5000 / q below 50, else 200 - 2 q; entry = clamp((t s + 50) / 100, 1, 255)),
+ * quality 1 .. 100; the Huffman tables are Annex K.3.3's.  Each component predicts its DC from the previous block in raster order,
+ * from 0 at the start of every frame; frames do not depend on each other.
+ * r2l_mjpeg_tables: the two quantisers in zig-zag order, as DQT stores them (host only).  r2l_mjpeg_header: the bytes in front of the
+ * scan, SOI APP0 (JFIF 1.01) DQT DQT SOF0 DHT x 4 SOS, into out_host (room for cap bytes); returns their number, 623 (host only).
+ * r2l_mjpeg_max_frame_bytes: a bound on header + byte-stuffed scan + EOI.  r2l_mjpeg_workspace_bytes: what r2l_mjpeg_encode needs for
+ * n_img frames at once.  All three return a negative code on a bad argument.
+ * r2l_mjpeg_encode: out_dev + k * out_pitch holds frame k's file (FF D8 ... FF D9), sizes_dev[k] (int64) its length; out_pitch at
+ * least r2l_mjpeg_max_frame_bytes.  coef_dev, int16 [n_img, n_blocks, 3, 64] or NULL: the quantised coefficients in zig-zag order, the DC
+ * before prediction, blocks in raster order.  Nothing is allocated or copied; the launches go to `stream`, the only atomic is an OR
+ * into cleared words, so the same input gives the same bytes.  H and W from 1 to 65535, n_img up to 65535, rgb_dev 4-byte, sizes_dev 8-byte,
+ * workspace_dev and coef_dev 16-byte aligned: R2L_EINVAL otherwise, before a device is touched.  n_img = 0 is a no-op. */
+int r2l_mjpeg_tables(int quality, unsigned char* luma64, unsigned char* chroma64);
+long long r2l_mjpeg_header(int H, int W, int quality, unsigned char* out_host, long long cap);
+long long r2l_mjpeg_workspace_bytes(int n_img, int H, int W);
+long long r2l_mjpeg_max_frame_bytes(int H, int W);
+int r2l_mjpeg_encode(const float* rgb_dev, int n_img, int H, int W, int quality, void* workspace_dev, long long workspace_bytes,
+                     unsigned char* out_dev, long long out_pitch, long long* sizes_dev, short* coef_dev, void* stream);
+
 /* ---- training of the NeRF teacher (csrc/nerf_train.hip; host mirror: efficient-nerf_amd/train_teacher.py) ----
  * A teacher step is the launches above (layers, embedding, scans, loss, Adam) plus the backward pass of nerf_raw2outputs[_noise]:
  * g_raw_dev [n,S,4] from g_rgb_map_dev [n,3], the only output the losses reach (main.py:728 detaches z_samples).  raw [n,S,4],
