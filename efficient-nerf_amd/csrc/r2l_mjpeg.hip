@@ -20,6 +20,7 @@
 
 #include "../../include/r2l_hip.h"
 #include "r2l_host_util.h"
+#include "r2l_to8b.h"
 
 namespace {
 
@@ -187,9 +188,6 @@ __global__ __launch_bounds__(256) void mjpeg_header_kernel(HeaderBytes hb, unsig
     for (int i = threadIdx.x; i < MJPEG_HEADER_BYTES; i += 256) o[i] = hb.b[i];
 }
 
-// frontend.to8b: floor(255 clamp(x, 0, 1)); fmaxf returns the other operand for a NaN, so a NaN is 0
-__device__ inline float mjpeg_byte(float x) { return floorf(255.0f * fminf(fmaxf(x, 0.0f), 1.0f)); }
-
 __global__ __launch_bounds__(256) void mjpeg_dct_kernel(const float* __restrict__ rgb, int H, int W, int bw, long long n_blocks, DctParams P,
                                                         short* __restrict__ coef) {
     __shared__ float s_c[64], s_q[2][64];
@@ -204,7 +202,7 @@ __global__ __launch_bounds__(256) void mjpeg_dct_kernel(const float* __restrict_
         const int by = (int)(b / bw), bx = (int)(b % bw);
         const int y = min(by * 8 + r8, H - 1), x = min(bx * 8 + c8, W - 1);      // replicate the last row and column
         const float* p = rgb + ((frame * H + y) * W + x) * 3;
-        const float R = mjpeg_byte(p[0]), G = mjpeg_byte(p[1]), B = mjpeg_byte(p[2]);
+        const float R = r2l_to8b(p[0]), G = r2l_to8b(p[1]), B = r2l_to8b(p[2]);
         s_f[wave][0][lane] = 0.299f * R + 0.587f * G + 0.114f * B - 128.0f;
         s_f[wave][1][lane] = -0.168736f * R - 0.331264f * G + 0.5f * B;
         s_f[wave][2][lane] = 0.5f * R - 0.418688f * G - 0.081312f * B;

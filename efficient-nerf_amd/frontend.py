@@ -101,6 +101,9 @@ FLAGS = [
     # the fly-through video (main.py:1096-1098, :1474-1499) as Motion-JPEG in an AVI file, encoded on the device (video.py, csrc/r2l_mjpeg.hip):
     # --render_only writes <outdir>/video[_<video_tag>].avi, training video_iter<i>[_<video_tag>].avi every --i_video iterations; off by default
     ('--write_video', dict(action=_BOOL)), ('--video_quality', dict(type=int, default=90)), ('--video_fps', dict(type=float, default=30)),
+    # the .png files of render_path and of the student's test renders finished on the device (png.py, csrc/r2l_png.hip) instead of by
+    # zlib on the host: the same pixels in other bytes; off by default
+    ('--png_device', dict(action=_BOOL)),
     # auto (default): fp16_fp8 (fp16 MFMA pass + bf6 correction terms, 1.7x the speed) when the checkpoint's own activation
     # ranges, measured on every ray of the first frame and watched on every frame after it, keep it inside the 1e-4 rgb
     # contract, fp16x3_asm otherwise (R2LEngine.choose_precision / check_ranges); the teacher measures fp16x1 (its layer chain as one
@@ -560,6 +563,9 @@ def build_engine(args, hwf, ckpt, probe_pose=None, probe_rays=None, log=None, pr
     raise R2LError(f'model_name={args.model_name} is not a render path of this build')
 
 
+PNG_FRAMES_PER_CALL = 8         # --png_device: render_path encodes this many frames at a time (fewer at the end)
+
+
 class _ImageWriter:
     """PNG encoding off the render loop (the reference writes with imageio inside its loop, main.py:337-341; here rank 0
     would hold the next collective while it deflates 1.9 MB in Python).  Frames are handed over as pinned host tensors whose
@@ -584,7 +590,11 @@ class _ImageWriter:
             try:
                 if ready is not None:
                     ready.synchronize()          # the event behind the D2H copy of this frame
-                write_png(path, to8b(img.numpy() if torch.is_tensor(img) else img))
+                if isinstance(img, tuple):       # --png_device: (slot, size) of a file finished on the device
+                    with open(path, 'wb') as f:
+                        f.write(img[0][:int(img[1])].numpy().tobytes())
+                else:
+                    write_png(path, to8b(img.numpy() if torch.is_tensor(img) else img))
             except Exception as e:               # surfaced by close()
                 self.err.append(e)
 
@@ -601,7 +611,7 @@ class _ImageWriter:
 
 
 def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=print, given_rays=None, frames_per_batch=None,
-                stats=None, watch_every=8, test_flip=False, lpips=None):
+                stats=None, watch_every=8, test_flip=False, lpips=None, png_device=False):
     """main.py:189-398 for the R2L and nerf branches: render, per-frame timing lines, PSNR / SSIM when GT is given.
 
     The loop is the one bench.py times ("batch >= 8 frames per collective"): frames go in batches of
@@ -763,6 +773,29 @@ def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=pr
     # the host copy of the frame stack, pinned, allocated once (a pinned allocation per batch cost 0.3 ms of every 10 ms frame):
     # every batch is copied into its slots on the side stream; the encoder threads and the caller (`stats['host_frames']`) read it
     host_stack = torch.empty((n_frames, H, W, 3), dtype=torch.float32, pin_memory=True) if writer is not None else None
+    png_enc = png_files = None
+    png_from = 0                    # --png_device: the first frame not yet encoded
+    if writer is not None and png_device and n_frames:
+        from .png import PNGEncoder
+        # a call's time hardly depends on its frames (one lane builds a segment's codes), so batches are collected up to PNG_FRAMES_PER_CALL
+        png_enc = PNGEncoder(H, W, max(B, PNG_FRAMES_PER_CALL), eng.device)
+        # the finished files of the frames, and of their ground truth behind them, pinned: one slot and one size each
+        png_files = (torch.empty((n_frames * (2 if gt_imgs is not None else 1), png_enc.pitch), dtype=torch.uint8, pin_memory=True),
+                     torch.empty(n_frames * (2 if gt_imgs is not None else 1), dtype=torch.int64, pin_memory=True))
+
+    def encode_on_side_stream(a, b):
+        """frames a .. b - 1 (and their ground truth) -> png_files, queued on the side stream; the worker threads write them behind its event"""
+        done = torch.cuda.Event()
+        with torch.cuda.stream(copy_stream):
+            for stack, at, tag in ((rgbs[a:b], a, ''),) + (((gt_imgs[a:b].to(rgbs.device, torch.float32).contiguous(), n_frames + a, '_gt'),)
+                                                           if gt_imgs is not None else ()):
+                slots, sizes = png_enc.launch(stack)
+                png_files[0][at:at + b - a].copy_(slots, non_blocking=True)
+                png_files[1][at:at + b - a].copy_(sizes, non_blocking=True)
+            done.record(copy_stream)
+        for f in range(a, b):
+            for at, tag in ((f, ''),) + (((n_frames + f, '_gt'),) if gt_imgs is not None else ()):
+                writer.put(os.path.join(savedir, f'{f:03d}{tag}.png'), (png_files[0][at], png_files[1][at]), done)
     mse_dev, ssim_dev = [], []
     n_coll = n_again = n_batches = 0
     check = (lambda: D.check_ranges(eng, log=log if rank == 0 else None)) if kind == 'R2L' else (lambda: None)
@@ -790,16 +823,23 @@ def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=pr
             with torch.cuda.stream(copy_stream):
                 host_stack[i0:i0 + nb].copy_(rgbs[i0:i0 + nb], non_blocking=True)
                 done.record(copy_stream)
-            for f in range(nb):
-                writer.put(os.path.join(savedir, f'{i0 + f:03d}.png'), host_stack[i0 + f], done)
+            if png_enc is None:
+                for f in range(nb):
+                    writer.put(os.path.join(savedir, f'{i0 + f:03d}.png'), host_stack[i0 + f], done)
+            elif i0 + nb - png_from + B > png_enc.n_max or i0 + nb == n_frames:
+                encode_on_side_stream(png_from, i0 + nb)
+                png_from = i0 + nb
         if gt_imgs is not None:
             for f in range(nb):
                 mse, ssim = frame_errors(rgbs[i0 + f], gt_imgs[i0 + f].to(rgbs.device))   # main.py:334-335
                 mse_dev.append(mse)
                 ssim_dev.append(ssim)
-                if writer is not None:  # main.py:340-341
+                if writer is not None and png_enc is None:  # main.py:340-341
                     writer.put(os.path.join(savedir, f'{i0 + f:03d}_gt.png'), gt_imgs[i0 + f].cpu().numpy())
-        torch.cuda.synchronize()       # the reference's per-frame bracket (main.py:273-310), once per batch here
+        if png_enc is None:
+            torch.cuda.synchronize()   # the reference's per-frame bracket (main.py:273-310), once per batch here
+        else:                          # ... around the render alone: the side stream's encodes run beside the next batches' renders
+            torch.cuda.current_stream().synchronize()
         if rank == 0:
             dt = (time.time() - t0) / nb
             for f in range(nb):
@@ -913,7 +953,7 @@ def main(argv=None):
     with torch.no_grad():
         rgbs, misc = render_path(poses, hwf, kind, eng, gt_imgs=gt, savedir=outdir, log=log, given_rays=given, stats=st,
                                  frames_per_batch=args.frames_per_batch or None, watch_every=args.watch_every, test_flip=args.test_flip,
-                                 lpips=lpips)
+                                 lpips=lpips, png_device=args.png_device)
     dt = time.time() - t_
     if rank == 0:
         np.save(os.path.join(outdir, 'rgbs.npy'), st['host_frames'].numpy() if 'host_frames' in st else rgbs.cpu().numpy())

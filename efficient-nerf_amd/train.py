@@ -527,10 +527,10 @@ def load_test_split(args, device=None):
     return (poses, (int(hwf[0]), int(hwf[1]), float(hwf[2])), gt if device is None else gt.to(device)), None
 
 
-def eval_test_split(trainer, test, savedir=None, test_flip=False, lpips=None):
+def eval_test_split(trainer, test, savedir=None, test_flip=False, lpips=None, png_device=False):
     """render_path over the test split from the live weights (main.py:1442-1456): the frames [N, H, W, 3] on the device and
-    frontend.test_metrics' test_psnr, test_psnr_v2 and test_ssim; with savedir the frames as <k>.png.  test: load_test_split's,
-    its ground truth on the trainer's device."""
+    frontend.test_metrics' test_psnr, test_psnr_v2 and test_ssim; with savedir the frames as <k>.png, with png_device finished on the
+    device from the stack where it lies (png.write_pngs).  test: load_test_split's, its ground truth on the trainer's device."""
     from .frontend import frame_errors, stack_flip, stack_lpips, test_metrics, to8b, write_png
     poses, (H, W, focal), gt = test
     rgbs = torch.empty((len(poses), H, W, 3), dtype=torch.float32, device=trainer.device)
@@ -549,6 +549,10 @@ def eval_test_split(trainer, test, savedir=None, test_flip=False, lpips=None):
         misc['test_flip'] = stack_flip(rgbs, gt)
     if savedir is not None:
         os.makedirs(savedir, exist_ok=True)
+        if png_device:
+            from .png import write_pngs
+            write_pngs([os.path.join(savedir, f'{k:03d}.png') for k in range(len(rgbs))], rgbs)
+            return rgbs, misc
         host = rgbs.cpu().numpy()
         for k in range(len(host)):
             write_png(os.path.join(savedir, f'{k:03d}.png'), to8b(host[k]))
@@ -677,7 +681,7 @@ def _train(args, log, engines):
 
     def test_pass(i):                         # main.py:1442-1456
         testsavedir = os.path.join(expdir, f'testset_iter{i}')
-        _, misc = eval_test_split(trainer, test, savedir=testsavedir, test_flip=flip_on, lpips=lpips)
+        _, misc = eval_test_split(trainer, test, savedir=testsavedir, test_flip=flip_on, lpips=lpips, png_device=getattr(args, 'png_device', False))
         flip_field = (f"TestLPIPS {misc['test_lpips']:.4f} " if lpips is not None else '') + (f"TestFLIP {misc['test_flip']:.4f} " if flip_on else '')
         return misc['test_psnr'], misc['test_psnr_v2'], f"TestSSIM {misc['test_ssim']:.4f} " + flip_field, f'Saved rendered test images: "{testsavedir}"'
 

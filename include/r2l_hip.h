@@ -619,6 +619,28 @@ long long r2l_mjpeg_max_frame_bytes(int H, int W);
 int r2l_mjpeg_encode(const float* rgb_dev, int n_img, int H, int W, int quality, void* workspace_dev, long long workspace_bytes,
                      unsigned char* out_dev, long long out_pitch, long long* sizes_dev, short* coef_dev, void* stream);
 
+/* ---- PNG files (csrc/r2l_png.hip; host side: efficient-nerf_amd/png.py) ----
+ * Each frame of rgb_dev, float32 [n_img, H, W, 3], becomes one complete PNG file: 8-bit RGB (colour type 2), non-interlaced, a byte
+ * p = floor(255 clamp(x, 0, 1)) as in the JPEG frames above (NaN = 0).  filter: -1 gives every row the type (None, Sub, Up, Average,
+ * Paeth) with the smallest sum of |residual as int8|, ties to the lowest type; 0 .. 4 forces that type on every row.  The filtered
+ * stream, H rows of 1 + 3 W bytes, is cut into segments of whole rows that are compressed independently of each other: matches are
+ * runs (distance 1, length 3 .. 258) that do not reach back over the segment's start, each segment is one deflate block with dynamic
+ * Huffman codes (lengths limited to 15 bits, 7 for the code-length code) or, where that is no shorter, one stored block; every segment
+ * but the last is closed with an empty stored block and is one IDAT chunk.  Adler-32 and every chunk's CRC-32 are computed on the device.
+ * r2l_png_layout: the rows of a segment (as many as give at most 16 KiB of filtered bytes, at least one) and the segments of a frame.
+ * r2l_png_max_frame_bytes: a bound on the file for any input (every segment stored).  r2l_png_workspace_bytes: what r2l_png_encode
+ * needs for n_img frames at once.  The two sizes return a negative code on a bad argument (host only, all three).
+ * r2l_png_encode: out_dev + k * pitch holds frame k's file, sizes_dev[k] (int64) its length; pitch at least r2l_png_max_frame_bytes.
+ * Nothing is allocated or copied and the host does not wait; the launches go to `stream`; the atomics are integer adds in LDS and ORs
+ * into cleared words, so the same input gives the same bytes, and a frame's file does not depend on the other frames.  H and W from 1 to
+ * 16384, n_img up to 65535, rgb_dev 4-byte, sizes_dev 8-byte, workspace_dev 16-byte aligned: R2L_EINVAL otherwise, before a device is
+ * touched.  n_img = 0 is a no-op. */
+long long r2l_png_max_frame_bytes(int H, int W);
+long long r2l_png_workspace_bytes(int n_img, int H, int W);
+int r2l_png_layout(int H, int W, int* rows_per_segment, int* n_segments);
+int r2l_png_encode(const float* rgb_dev, int n_img, int H, int W, int filter, void* workspace_dev, long long workspace_bytes,
+                   unsigned char* out_dev, long long pitch, long long* sizes_dev, void* stream);
+
 /* ---- training of the NeRF teacher (csrc/nerf_train.hip; host mirror: efficient-nerf_amd/train_teacher.py) ----
  * A teacher step is the launches above (layers, embedding, scans, loss, Adam) plus the backward pass of nerf_raw2outputs[_noise]:
  * g_raw_dev [n,S,4] from g_rgb_map_dev [n,3], the only output the losses reach (main.py:728 detaches z_samples).  raw [n,S,4],
