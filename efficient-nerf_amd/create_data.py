@@ -50,6 +50,7 @@ from . import _lib
 from . import dist as D
 from .frontend import pose_spherical, to8b, write_png
 from .teacher import get_rays
+from .watch import Watch
 
 
 class RandStream:
@@ -339,17 +340,6 @@ def build_llff_teacher_engine(args, ckpt, hwf, state, use_rand_focal=True, log=N
     return eng
 
 
-def _agree_failed(failed, world, dev):
-    """True on every rank when a shard write failed on ANY rank (one 4-byte all-reduce): the ranks raise together instead of
-    one raising while its peers wait for it inside the group's all-to-all"""
-    if world == 1:
-        return bool(failed)
-    import torch.distributed as tdist
-    t = torch.tensor([1 if failed else 0], dtype=torch.int32, device=dev if tdist.get_backend() == 'nccl' else 'cpu')
-    tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
-    return bool(t.item())
-
-
 class ShardWriteError(OSError):
     """a `data_{k}.npy` could not be written (this rank's own error is the __cause__; on the other ranks: which rank reported)"""
 
@@ -408,7 +398,9 @@ def create_rand(engine, H, W, focal, n_pose_kd, datadir_new, use_rand_focal=True
     i_done = 0
 
     def raise_if_write_failed():
-        if _agree_failed(bool(writer.err), world, dev):
+        # a shard write that failed on ANY rank (one 4-byte all-reduce): the ranks raise together instead of one raising while its
+        # peers wait for it inside the group's all-to-all
+        if D.any_rank(bool(writer.err), dev):
             planner.stop()
             writer.close(raise_errors=False)
             if writer.err:
@@ -420,63 +412,54 @@ def create_rand(engine, H, W, focal, n_pose_kd, datadir_new, use_rand_focal=True
     # engine.WATCH_RAYS of its rays (rgb / acc / depth: < 0.5 % of the group's work).  A miss moves EVERY rank one rung down the
     # ladder and the group is rendered again.
     watching = bool(watch) and hasattr(engine, 'spot_check')
-    wstat = {'checks': 0, 'fallbacks': [], 'worst': {}}
+    w = Watch(len(engine.LADDER) if watching else 0, log=log, device=dev)
     if hasattr(engine, 'set_skip_rgb0'):
         # the shards hold [rays_o, rays_d, rgb] (utils/create_data.py:832-836; `rgb, disp, acc, _ = render(...)` :824-831): nobody takes rgb0,
         # so the coarse pass runs without its view branch where its mode has that build (fp16x3_asm): the same rgb bit for bit
         engine.set_skip_rgb0(True)
 
     def render_pose(i, pose, focal_, j, check):
+        """pose i into slot j of the slab; the spot check's (ok, differences) when it is checked in a fast mode, else None"""
         rays_o, rays_d = get_rays_fn(H, W, focal_, pose[:3, :4], device=dev)  # get_rays1 (:819)
         ro, rd = rays_o.reshape(-1, 3), rays_d.reshape(-1, 3)
         out = engine.render_rays(ro, rd)
-        miss = None
-        if check:
-            ok, d = engine.spot_check(ro, rd, out)
-            wstat['checks'] += 1
-            for k, v in d.items():
-                wstat['worst'][k] = max(wstat['worst'].get(k, 0.), v)
-            miss = None if ok else d
+        verdict = engine.spot_check(ro, rd, out) if check and engine.precision_name != 'fp16x3' else None
         torch.cat([ro, rd, out['rgb_map']], dim=-1, out=slab[j // world])  # [H*W, 9]
         if i <= save_png:
             img = out['rgb_map'].view(H, W, 3).cpu().numpy()
             path = os.path.join(datadir_new, f'pseudo_sample_{i}.png')
             writer.put(lambda img=img, path=path: write_png(path, to8b(img)))
-        return miss
+        return verdict
 
     def render_group(grp):
-        """this rank's poses of the group into the slab; the spot check's differences when its first pose missed, else None"""
-        miss, first = None, True
+        """this rank's poses of the group into the slab; the spot check of the first of them (render_pose)"""
+        verdict, first = None, True
         for i, pose, focal_ in grp:
             j = (i - 1) % i_save                            # index inside the save group
             if j % world != rank:
                 continue
-            check = watching and first and engine.precision_name != 'fp16x3'
-            m = render_pose(i, pose, focal_, j, check)
-            while world == 1 and m is not None:             # one rank: act at once, only this pose is rendered again
-                step_down(i, m)
-                m = render_pose(i, pose, focal_, j, engine.precision_name != 'fp16x3')
-            miss = miss or m
-            first = False
-        return miss
+            v = render_pose(i, pose, focal_, j, watching and first)
+            if first and watching and world == 1:           # one rank: act at once, only this pose is rendered again
+                w.run(v, check=lambda v: v, step_down=step_down(i), again=lambda: render_pose(i, pose, focal_, j, True))
+            verdict, first = verdict or v, False
+        return verdict
 
-    def step_down(i, d):
-        was = engine.precision_name
-        now = engine.step_down()
-        wstat['fallbacks'].append({'pose': i, 'from': was, 'to': now, 'diffs': d})
-        log(f'[precision] pose {i}: {was} is {d} from fp16x3 on {engine.WATCH_RAYS} of its rays -> {now}; rendered again')
+    def step_down(i):
+        def down(ok, d):
+            was = engine.precision_name
+            now = engine.step_down()
+            d = d if not ok else 'another rank\'s pose'
+            return ({'pose': i, 'from': was, 'to': now, 'diffs': d},
+                    f'[precision] pose {i}: {was} is {d} from fp16x3 on {engine.WATCH_RAYS} of its rays -> {now}; rendered again')
+        return down
 
     while i_done < n_pose_kd:
         if world == 1:
             raise_if_write_failed()
         (grp,) = planner.get('poses')
-        miss = render_group(grp)
-        if watching and world > 1:
-            for _ in range(len(engine.LADDER)):
-                if not _agree_failed(miss is not None, world, dev):
-                    break
-                step_down(grp[0][0], miss or 'another rank\'s pose')      # every rank, together
-                miss = render_group(grp)
+        verdict = render_group(grp)
+        if watching and world > 1:      # several ranks: agreed after the group, every rank steps down and renders its share of the group again
+            w.run(verdict, check=lambda v: v, step_down=step_down(grp[0][0]), again=lambda: render_group(grp))
         i_done = grp[-1][0]
         if len(grp) < i_save:
             break        # the remainder of the last group is rendered and never flushed, as in the reference (:855)
@@ -553,7 +536,7 @@ def create_rand(engine, H, W, focal, n_pose_kd, datadir_new, use_rand_focal=True
                        shards=split - first_split, planner_busy_s=planner.busy_s, permutation_s=planner.perm_s,
                        writer_busy_s=writer.busy_s, writer_threads=writer_threads)
         if watching:
-            timings['watch'] = dict(wstat, precision=engine.precision_name)
+            timings['watch'] = dict(w.stats(), precision=engine.precision_name)
         if tail_from is not None:
             # what follows the last group's last render: its shuffle, exchange, copy and file writes -- the only ones nothing overlaps
             timings['tail_s'] = t_end - tail_from

@@ -34,6 +34,8 @@ import zlib
 import numpy as np
 import torch
 
+from .watch import Watch
+
 # ----------------------------------------------------------------------------------------
 # flags (subset of option.py that the render-only hot path reads; same names, same defaults)
 # ----------------------------------------------------------------------------------------
@@ -121,7 +123,8 @@ FLAGS = [
     ('--watch_every', dict(type=int, default=8)),
     # N > 1 without torchrun: main.py / create_data.py start the N ranks themselves before importing torch (launch.py)
     ('--gpus', dict(type=int, default=0)), ('--launch_timeout', dict(type=float, default=0.)),
-    # training on several ranks: the seed every rank gives numpy's and torch's generators at start-up (-1: a draw from rank 0's stream)
+    # training on several ranks: the seed every rank gives numpy's and torch's generators at start-up (-1: a draw from rank 0's stream);
+    # train_teacher.py, which is one process: >= 0 seeds that process, -1 leaves its generators as they are
     ('--dist_seed', dict(type=int, default=-1)),
 ]
 
@@ -610,6 +613,165 @@ class _ImageWriter:
             raise self.err[0]
 
 
+class _PictureSink:
+    """The picture side of render_path (rank 0 with a savedir): every batch of the frame stack `rgbs` is copied into the pinned
+    `host_stack` on a side stream behind the gather, and its frames and their ground truth become `<i>.png` / `<i>_gt.png` (main.py:337-341) on
+    _ImageWriter's threads, which wait for the event behind the copy -- the loop does not.  png_device: the files are finished on the
+    device instead (png.PNGEncoder on the side stream, up to PNG_FRAMES_PER_CALL frames a call) and the threads only write them."""
+
+    def __init__(self, savedir, rgbs, gt_imgs, B, png_device):
+        n_frames, H, W, _ = rgbs.shape
+        self.savedir, self.rgbs, self.gt, self.B = savedir, rgbs, gt_imgs, B
+        self.writer = _ImageWriter()
+        self.stream = torch.cuda.Stream(device=rgbs.device)
+        # the host copy of the frame stack, pinned, allocated once (a pinned allocation per batch cost 0.3 ms of every 10 ms frame):
+        # the encoder threads and the caller (`stats['host_frames']`) read it
+        self.host_stack = torch.empty((n_frames, H, W, 3), dtype=torch.float32, pin_memory=True)
+        self.enc = self.files = None
+        self.encoded = 0                # --png_device: the first frame not yet encoded
+        if png_device and n_frames:
+            from .png import PNGEncoder
+            # a call's time hardly depends on its frames (one lane builds a segment's codes), so batches are collected up to PNG_FRAMES_PER_CALL
+            self.enc = PNGEncoder(H, W, max(B, PNG_FRAMES_PER_CALL), rgbs.device)
+            # the finished files of the frames, and of their ground truth behind them, pinned: one slot and one size each
+            n_files = n_frames * (2 if gt_imgs is not None else 1)
+            self.files = (torch.empty((n_files, self.enc.pitch), dtype=torch.uint8, pin_memory=True), torch.empty(n_files, dtype=torch.int64, pin_memory=True))
+
+    def _path(self, f, tag=''):
+        return os.path.join(self.savedir, f'{f:03d}{tag}.png')
+
+    def put(self, i0, nb):
+        """frames i0 .. i0 + nb - 1 are in the stack (on the current stream)"""
+        done = torch.cuda.Event()
+        self.stream.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(self.stream):
+            self.host_stack[i0:i0 + nb].copy_(self.rgbs[i0:i0 + nb], non_blocking=True)
+            done.record(self.stream)
+        if self.enc is None:
+            for f in range(i0, i0 + nb):
+                self.writer.put(self._path(f), self.host_stack[f], done)
+            if self.gt is not None:
+                for f in range(i0, i0 + nb):
+                    self.writer.put(self._path(f, '_gt'), self.gt[f].cpu().numpy())
+        elif i0 + nb - self.encoded + self.B > self.enc.n_max or i0 + nb == len(self.rgbs):
+            self._encode(self.encoded, i0 + nb)
+            self.encoded = i0 + nb
+
+    def _encode(self, a, b):
+        """frames a .. b - 1 (and their ground truth) -> files, queued on the side stream; the worker threads write them behind its event"""
+        n_frames = len(self.rgbs)
+        stacks = ((self.rgbs[a:b], a, ''),)
+        if self.gt is not None:
+            stacks += ((self.gt[a:b].to(self.rgbs.device, torch.float32).contiguous(), n_frames + a, '_gt'),)
+        done = torch.cuda.Event()
+        with torch.cuda.stream(self.stream):
+            for stack, at, _ in stacks:
+                slots, sizes = self.enc.launch(stack)
+                self.files[0][at:at + b - a].copy_(slots, non_blocking=True)
+                self.files[1][at:at + b - a].copy_(sizes, non_blocking=True)
+            done.record(self.stream)
+        for f in range(a, b):
+            for _, at, tag in stacks:
+                self.writer.put(self._path(f, tag), (self.files[0][at + f - a], self.files[1][at + f - a]), done)
+
+    def close(self):
+        self.writer.close()
+
+
+class _TeacherWatch(Watch):
+    """render_path's watch of the teacher's fast modes: fp16x1 / fp16_fp8 / fp16_mix were chosen on a probe; a watched
+    frame is checked against fp16x3 on a sample of its own rays (rays_of(i): this rank's), agreed between the ranks (every rank checks
+    the same frames, so all act alike), with fallback + re-render, for as many rungs as the ladder has.  log: rank 0's, None elsewhere."""
+
+    def __init__(self, eng, log, rays_of):
+        super().__init__(len(eng.LADDER), log=log, device=eng.device)
+        self.eng, self.rays_of = eng, rays_of
+
+    def frame(self, i, rays, got, render):
+        """got = render() is frame i, of `rays` when they were given; returns the frame to hand on"""
+        eng = self.eng
+
+        def check(got):
+            nonlocal rays
+            rays = rays if rays is not None else self.rays_of(i)
+            return eng.spot_check(*rays, got)
+
+        def step_down(ok, d):
+            was, now = eng.precision_name, eng.step_down()
+            return ({'frame': i, 'from': was, 'to': now, 'diffs': d},
+                    f'[precision] frame {i}: {was} is {d} from fp16x3 on {eng.WATCH_RAYS} of its rays (limits '
+                    f'{eng.AUTO_MAX_DIFF_X1 if was == "fp16x1" else eng.AUTO_MAX_DIFF:.0e} x (1, 1, far)) -> {now}; frame rendered again')
+
+        # fp16x3 is the mode the watch compares with (fp16x3_asm is watched too since round 6)
+        return self.run(got, check, step_down, again=render, live=lambda: eng.precision_name != 'fp16x3')
+
+
+class _StudentWatch(Watch):
+    """render_path's rgb watch of every rung `auto` can choose for the R2L student (R2LEngine.spot_check_rgb): the split rungs -- `auto`
+    measured on the probe frames how many leading blocks need three passes -- every watch_every-th batch (a sample of the rank's own rays of
+    the batch's first frame with the split and with three passes everywhere; a miss on any rank moves half of the low-precision part to
+    three passes on every rank); the whole-network rungs fp16_fp8 / fp16_e4m3 (round 6) every WHOLE_WATCH_EVERY-th batch against a second
+    context holding the weights in three passes (a miss sends the network to the measured split rungs: rank 0's choice on every
+    rank, then checked on every rank's rays by the same loop).  The batch is rendered again after every change."""
+
+    def __init__(self, eng, log, rays_of, every):
+        super().__init__(6, log=log, device=eng.device, worst=0.0)
+        self.eng, self.rays_of, self.every = eng, rays_of, every
+        self.on = every > 0 and hasattr(eng, 'spot_check_rgb')
+        self.whole_every = max(1, int(getattr(eng, 'WHOLE_WATCH_EVERY', 16) * every / 8)) if every > 0 else 0
+
+    def due(self, n_batches):
+        mode = self.eng.watched_mode() if self.on else None
+        return (mode == 'split' and n_batches % self.every == 0) or (mode == 'whole' and n_batches % self.whole_every == 0)
+
+    def batch(self, i0, again):
+        """watches the batch whose first frame is i0; again() renders it again; returns how often it did"""
+        from . import dist as D
+        eng = self.eng
+        mode = rays = None
+
+        def check(_):
+            # every rank enters the collective whatever its local mode is (ADVICE r5: a rank that had left the rung would otherwise
+            # miss the all-reduce its peers are in); a rank with nothing to watch reports "good"
+            nonlocal mode, rays
+            mode = eng.watched_mode()
+            if mode is None:
+                return None
+            rays = self.rays_of(i0)
+            return eng.spot_check_rgb(*rays)
+
+        def step_down(ok, d):
+            d = 0.0 if d is None else d
+            was_mode, was = eng.precision_name, eng.split_block
+            limit, n_w = eng.SPLIT_WATCH_MAX_DIFF, eng.SPLIT_WATCH_RAYS
+            if mode == 'whole':
+                eng.step_down_whole(*rays)
+                D.agree_precision(eng)                 # rank 0's measured rung on every rank; the loop checks it on every rank's rays next
+                limit, n_w = eng.WHOLE_WATCH_MAX_DIFF, eng.WHOLE_WATCH_RAYS
+            elif mode == 'split':
+                eng.step_down_split()
+            # (neither: a peer missed; this rank follows its rung, which steps down deterministically from the shared state)
+            now = eng.precision_name
+            to = f'{now} at block {eng.split_block}' if now.startswith('fp16_split') else now
+            what = f'with low-precision terms from block {was} on' if mode == 'split' else f'{was_mode} is'
+            return ({'frame': i0, 'from': was_mode, 'split': was, 'to': eng.split_block if now.startswith('fp16_split') else now, 'diff': d},
+                    f'[precision] frame {i0}: {what} {d:.1e} from three passes on {n_w} of its rays (limit {limit:g}) -> {to}; batch rendered again')
+
+        before = len(self.fallbacks)
+        self.run(None, check, step_down, again)
+        return len(self.fallbacks) - before
+
+
+def _rank_rays(given_rays, render_poses, i, hwf, rows, device):
+    """(rays_o, rays_d), each [(r1 - r0) * W, 3] float32 on the device: rows [r0, r1) of frame i, out of given_rays when there are any, else
+    the camera rays of pose i"""
+    H, W, focal = hwf
+    if given_rays is not None:
+        return tuple(g[i].reshape(H, W, 3)[rows[0]:rows[1]].reshape(-1, 3).contiguous().to(device, torch.float32) for g in given_rays)
+    from .teacher import get_rays
+    return tuple(t.reshape(-1, 3) for t in get_rays(H, W, focal, torch.as_tensor(render_poses[i])[:3, :4], rows=rows, device=device))
+
+
 def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=print, given_rays=None, frames_per_batch=None,
                 stats=None, watch_every=8, test_flip=False, lpips=None, png_device=False):
     """main.py:189-398 for the R2L and nerf branches: render, per-frame timing lines, PSNR / SSIM when GT is given.
@@ -619,20 +781,18 @@ def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=pr
     the batch in one launch (`render_batch`: world x H/world rows = one frame's worth of ray tiles per rank, the grid bench.py
     fills), ONE `r2l_gather_image` assembles them straight into the frame stack, the range check (one all-reduce) runs once
     per batch, and the host synchronises once per batch for the reference's timing line.  PNGs are encoded on worker threads
-    from pinned host copies made on a side stream; PSNR / SSIM stay on the device until the loop is over.
+    from pinned host copies made on a side stream (_PictureSink); PSNR / SSIM stay on the device until the loop is over.
     `given_rays` = (all_rays_o, all_rays_d) [N, H*W, 3] replaces the camera rays (--given_render_path_rays,
     main.py:207-230: the DONERF test path through PointSampler.sample_train).
     `stats` (dict, optional) receives the loop's own numbers: render_loop_s (first launch to last sync, image encoding
     excluded), batches, collectives, rerenders.
-    Teacher frames in a fast mode (fp16x1 / fp16_fp8, chosen once by `--precision auto` or by flag) are watched: every
+    Teacher frames in a fast mode (chosen once by `--precision auto` or by flag) are watched (watch.Watch): every
     `watch_every`-th frame (and the first) a rank re-renders NeRFEngine.WATCH_RAYS of its rays in fp16x3 and compares rgb / acc /
-    depth (NeRFEngine.spot_check); a miss on any rank moves every rank one rung down the ladder and the frame is rendered
-    again (`stats['watch']`).  0 switches the watch off."""
+    depth (NeRFEngine.spot_check); a miss on any rank moves every rank one rung down the ladder and the frame is rendered and
+    checked again, down to fp16x3 (`stats['watch']`).  0 switches the watch off."""
     from . import dist as D
-    import torch.distributed as tdist
     H, W, focal = hwf
-    world = tdist.get_world_size() if tdist.is_initialized() else 1
-    rank = tdist.get_rank() if tdist.is_initialized() else 0
+    rank, world = D.rank_world()
     r0, r1 = D.row_shard(H, rank, world)
     n_local = (r1 - r0) * W
     n_frames = len(given_rays[0]) if given_rays is not None else len(render_poses)
@@ -645,6 +805,9 @@ def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=pr
     if given_rays is None and kind == 'R2L' and n_frames:
         pose_dev = torch.stack([torch.as_tensor(p)[:3, :4].float() for p in render_poses], 0).contiguous().to(eng.device)
 
+    def rank_rays(i):
+        return _rank_rays(given_rays, render_poses, i, hwf, (r0, r1), eng.device)
+
     def render_local(i0, nb):
         """row shard of frames i0 .. i0 + nb - 1 into local[:nb] (one rank: straight into the frame stack, nothing to assemble)"""
         dst = local[:nb] if world > 1 else rgbs[i0:i0 + nb].view(nb, n_local, 3)
@@ -653,80 +816,15 @@ def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=pr
             return
         for f in range(nb):
             i = i0 + f
-            ro = rd = None
-            if given_rays is not None:
-                ro = given_rays[0][i].reshape(H, W, 3)[r0:r1].reshape(-1, 3).contiguous().to(eng.device, torch.float32)
-                rd = given_rays[1][i].reshape(H, W, 3)[r0:r1].reshape(-1, 3).contiguous().to(eng.device, torch.float32)
-                got = eng.render_rays(ro, rd)
-            else:
-                got = eng.render(render_poses[i][:3, :4], rows=(r0, r1))
-            if watching and i % watch_every == 0:
-                got = watched(i, ro, rd, got)
+            rays = rank_rays(i) if given_rays is not None else None
+            render = (lambda: eng.render_rays(*rays)) if rays is not None else (lambda: eng.render(render_poses[i][:3, :4], rows=(r0, r1)))
+            got = render()
+            if teacher is not None and i % watch_every == 0:
+                got = teacher.frame(i, rays, got, render)
             dst[f].copy_(got if kind == 'R2L' else got['rgb_map'])
 
-    # every rung `auto` can choose for the R2L student under an rgb watch (R2LEngine.spot_check_rgb): the split rungs -- `auto` measured on
-    # the probe frames how many leading blocks need three passes -- every watch_every-th batch (a sample of the rank's own rays of the
-    # batch's first frame with the split and with three passes everywhere; a miss on any rank moves half of the low-precision part to
-    # three passes on every rank); the whole-network rungs fp16_fp8 / fp16_e4m3 (round 6) every WHOLE_WATCH_EVERY-th batch against a second
-    # context holding the weights in three passes (a miss sends the network to the measured split rungs: rank 0's choice on every
-    # rank, then checked on every rank's rays by the same loop).  The batch is rendered again after every change.
-    split_watching = kind == 'R2L' and watch_every > 0 and hasattr(eng, 'spot_check_rgb')
-    split_watch = {'checks': 0, 'fallbacks': [], 'worst': 0.0}
-    whole_every = max(1, int(getattr(eng, 'WHOLE_WATCH_EVERY', 16) * watch_every / 8)) if watch_every > 0 else 0
-
-    def watch_due(n_batches):
-        mode = eng.watched_mode() if split_watching else None
-        return (mode == 'split' and n_batches % watch_every == 0) or (mode == 'whole' and n_batches % whole_every == 0)
-
-    def watch_split(i0, nb):
-        from .teacher import get_rays
-        again = 0
-        for _ in range(6):
-            # every rank enters the collective whatever its local mode is (a rank that had left the rung would otherwise
-            # miss the all-reduce its peers are in); a rank with nothing to watch reports "good"
-            mode = eng.watched_mode()
-            ok, d = True, 0.0
-            if mode is not None:
-                if given_rays is not None:
-                    ro = given_rays[0][i0].reshape(H, W, 3)[r0:r1].reshape(-1, 3).contiguous().to(eng.device, torch.float32)
-                    rd = given_rays[1][i0].reshape(H, W, 3)[r0:r1].reshape(-1, 3).contiguous().to(eng.device, torch.float32)
-                else:
-                    ro, rd = (t.reshape(-1, 3) for t in get_rays(H, W, focal, torch.as_tensor(render_poses[i0])[:3, :4], rows=(r0, r1), device=eng.device))
-                ok, d = eng.spot_check_rgb(ro, rd)
-                split_watch['checks'] += 1
-                split_watch['worst'] = max(split_watch['worst'], d)
-            bad = 0 if ok else 1
-            if world > 1:
-                t = torch.tensor([bad], dtype=torch.int32, device=eng.device if tdist.get_backend() == 'nccl' else 'cpu')
-                tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
-                bad = int(t.item())
-            if not bad:
-                break
-            was_mode, was = eng.precision_name, eng.split_block
-            if mode == 'whole':
-                now = eng.step_down_whole(ro, rd)
-                D.agree_precision(eng)                 # rank 0's measured rung on every rank; the loop checks it on every rank's rays next
-                now = eng.precision_name
-                limit, n_w = eng.WHOLE_WATCH_MAX_DIFF, eng.WHOLE_WATCH_RAYS
-            elif mode == 'split':
-                now = eng.step_down_split()
-                limit, n_w = eng.SPLIT_WATCH_MAX_DIFF, eng.SPLIT_WATCH_RAYS
-            else:                                      # a peer missed: follow its rung (it steps down deterministically from the shared state)
-                now = eng.precision_name
-                limit, n_w = eng.SPLIT_WATCH_MAX_DIFF, eng.SPLIT_WATCH_RAYS
-            split_watch['fallbacks'].append({'frame': i0, 'from': was_mode, 'split': was, 'to': eng.split_block if now.startswith('fp16_split') else now, 'diff': d})
-            if rank == 0:
-                what = f'with low-precision terms from block {was} on' if mode == 'split' else f'{was_mode} is'
-                log(f'[precision] frame {i0}: {what} {d:.1e} from three passes on {n_w} of its rays (limit {limit:g}) -> ' +
-                    (f'{now} at block {eng.split_block}' if now.startswith('fp16_split') else now) + '; batch rendered again')
-            eng.render_checked(lambda: render_local(i0, nb), check=check)
-            again += 1
-        return again
-
-    # the teacher's fast modes under watch: fp16x1 / fp16_fp8 were chosen on a probe; every watch_every-th
-    # frame is checked against fp16x3 on a sample of its own rays, agreed between the ranks, with fallback + re-render
-    watching = kind != 'R2L' and watch_every > 0 and hasattr(eng, 'spot_check')
-    watch = {'checks': 0, 'fallbacks': [], 'worst': {}}
+    student = _StudentWatch(eng, log if rank == 0 else None, rank_rays, watch_every) if kind == 'R2L' else None
+    teacher = _TeacherWatch(eng, log if rank == 0 else None, rank_rays) if kind != 'R2L' and watch_every > 0 and hasattr(eng, 'spot_check') else None
     if kind != 'R2L' and hasattr(eng, 'set_skip_rgb0'):
         # this loop keeps rgb only (main.py:277-282 drops render()'s extras): the coarse pass runs without its view branch when its mode has
         # that build (fp16x3_asm, the coarse mode of every trained teacher) -- bit for bit the same frames, 17 % fewer coarse MACs
@@ -734,71 +832,15 @@ def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=pr
         if rank == 0 and eng._rgb0_skipped():
             log('[precision] rgb only: the coarse pass runs without its view branch and fine-pass tiles without a positive density skip theirs '
                 '(rgb0 is not produced; rgb / disp / acc are bit for bit the same)')
-
-    def watched(i, ro, rd, got):
-        from .teacher import get_rays
-        for _ in range(3):
-            if eng.precision_name == 'fp16x3':          # the mode the watch compares with (fp16x3_asm is watched too since round 6)
-                break
-            if ro is None:
-                ro, rd = (t.reshape(-1, 3) for t in get_rays(H, W, focal, torch.as_tensor(render_poses[i])[:3, :4], rows=(r0, r1),
-                                                             device=eng.device))
-            ok, d = eng.spot_check(ro, rd, got)
-            watch['checks'] += 1
-            for k, v in d.items():
-                watch['worst'][k] = max(watch['worst'].get(k, 0.), v)
-            bad = 0 if ok else 1
-            if world > 1:     # every rank checks the same frames: one 4-byte all-reduce per check, all ranks act alike
-                t = torch.tensor([bad], dtype=torch.int32, device=eng.device if tdist.get_backend() == 'nccl' else 'cpu')
-                tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
-                bad = int(t.item())
-            if not bad:
-                break
-            was = eng.precision_name
-            now = eng.step_down()
-            watch['fallbacks'].append({'frame': i, 'from': was, 'to': now, 'diffs': d})
-            if rank == 0:
-                log(f'[precision] frame {i}: {was} is {d} from fp16x3 on {eng.WATCH_RAYS} of its rays (limits '
-                    f'{eng.AUTO_MAX_DIFF_X1 if was == "fp16x1" else eng.AUTO_MAX_DIFF:.0e} x (1, 1, far)) -> {now}; frame rendered again')
-            got = eng.render_rays(ro, rd) if given_rays is not None else eng.render(render_poses[i][:3, :4], rows=(r0, r1))
-        return got
-
     if kind == 'R2L' and world > 1 and n_frames > 0:
         # an explicit fp16_fp8 measures its activation ranges on the first render's own rays: one agreed set for all row
         # shards (`auto` has measured every ray of a whole frame on every rank already, the all-reduce then only confirms it)
         render_local(0, 1)
         D.agree_act_exponents(eng)
-    writer = _ImageWriter() if (savedir is not None and rank == 0) else None
-    copy_stream = torch.cuda.Stream(device=eng.device) if writer is not None else None
-    # the host copy of the frame stack, pinned, allocated once (a pinned allocation per batch cost 0.3 ms of every 10 ms frame):
-    # every batch is copied into its slots on the side stream; the encoder threads and the caller (`stats['host_frames']`) read it
-    host_stack = torch.empty((n_frames, H, W, 3), dtype=torch.float32, pin_memory=True) if writer is not None else None
-    png_enc = png_files = None
-    png_from = 0                    # --png_device: the first frame not yet encoded
-    if writer is not None and png_device and n_frames:
-        from .png import PNGEncoder
-        # a call's time hardly depends on its frames (one lane builds a segment's codes), so batches are collected up to PNG_FRAMES_PER_CALL
-        png_enc = PNGEncoder(H, W, max(B, PNG_FRAMES_PER_CALL), eng.device)
-        # the finished files of the frames, and of their ground truth behind them, pinned: one slot and one size each
-        png_files = (torch.empty((n_frames * (2 if gt_imgs is not None else 1), png_enc.pitch), dtype=torch.uint8, pin_memory=True),
-                     torch.empty(n_frames * (2 if gt_imgs is not None else 1), dtype=torch.int64, pin_memory=True))
-
-    def encode_on_side_stream(a, b):
-        """frames a .. b - 1 (and their ground truth) -> png_files, queued on the side stream; the worker threads write them behind its event"""
-        done = torch.cuda.Event()
-        with torch.cuda.stream(copy_stream):
-            for stack, at, tag in ((rgbs[a:b], a, ''),) + (((gt_imgs[a:b].to(rgbs.device, torch.float32).contiguous(), n_frames + a, '_gt'),)
-                                                           if gt_imgs is not None else ()):
-                slots, sizes = png_enc.launch(stack)
-                png_files[0][at:at + b - a].copy_(slots, non_blocking=True)
-                png_files[1][at:at + b - a].copy_(sizes, non_blocking=True)
-            done.record(copy_stream)
-        for f in range(a, b):
-            for at, tag in ((f, ''),) + (((n_frames + f, '_gt'),) if gt_imgs is not None else ()):
-                writer.put(os.path.join(savedir, f'{f:03d}{tag}.png'), (png_files[0][at], png_files[1][at]), done)
+    sink = _PictureSink(savedir, rgbs, gt_imgs, B, png_device) if (savedir is not None and rank == 0) else None
     mse_dev, ssim_dev = [], []
     n_coll = n_again = n_batches = 0
-    check = (lambda: D.check_ranges(eng, log=log if rank == 0 else None)) if kind == 'R2L' else (lambda: None)
+    check_ranges = (lambda: D.check_ranges(eng, log=log if rank == 0 else None)) if kind == 'R2L' else (lambda: None)
     torch.cuda.synchronize()
     t_loop = time.time()
     for i0 in range(0, n_frames, B):
@@ -807,36 +849,24 @@ def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=pr
         if kind == 'R2L':
             # did this batch's rays stay inside the range the low-precision scales were measured for?  If not: measured,
             # raised, or the context falls back (`auto`), and the batch is rendered again -- one check per batch
-            _, again = eng.render_checked(lambda: render_local(i0, nb), check=check)
+            _, again = eng.render_checked(lambda: render_local(i0, nb), check=check_ranges)
             n_again += again
-            if watch_due(n_batches):
-                n_again += watch_split(i0, nb)
+            if student.due(n_batches):
+                n_again += student.batch(i0, lambda: eng.render_checked(lambda: render_local(i0, nb), check=check_ranges))
         else:
             render_local(i0, nb)
         if world > 1:
             D.gather_rows(local[:nb], H, W, world, out=rgbs[i0:i0 + nb])
             n_coll += 1
         n_batches += 1
-        if writer is not None:      # D2H on a side stream behind the gather; the worker waits for the event, the loop does not
-            done = torch.cuda.Event()
-            copy_stream.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(copy_stream):
-                host_stack[i0:i0 + nb].copy_(rgbs[i0:i0 + nb], non_blocking=True)
-                done.record(copy_stream)
-            if png_enc is None:
-                for f in range(nb):
-                    writer.put(os.path.join(savedir, f'{i0 + f:03d}.png'), host_stack[i0 + f], done)
-            elif i0 + nb - png_from + B > png_enc.n_max or i0 + nb == n_frames:
-                encode_on_side_stream(png_from, i0 + nb)
-                png_from = i0 + nb
+        if sink is not None:
+            sink.put(i0, nb)
         if gt_imgs is not None:
             for f in range(nb):
                 mse, ssim = frame_errors(rgbs[i0 + f], gt_imgs[i0 + f].to(rgbs.device))   # main.py:334-335
                 mse_dev.append(mse)
                 ssim_dev.append(ssim)
-                if writer is not None and png_enc is None:  # main.py:340-341
-                    writer.put(os.path.join(savedir, f'{i0 + f:03d}_gt.png'), gt_imgs[i0 + f].cpu().numpy())
-        if png_enc is None:
+        if sink is None or sink.enc is None:
             torch.cuda.synchronize()   # the reference's per-frame bracket (main.py:273-310), once per batch here
         else:                          # ... around the render alone: the side stream's encodes run beside the next batches' renders
             torch.cuda.current_stream().synchronize()
@@ -845,17 +875,17 @@ def render_path(render_poses, hwf, kind, eng, gt_imgs=None, savedir=None, log=pr
             for f in range(nb):
                 log(f'[#{i0 + f}] frame, rendering done, time for this frame: {dt:.4f}s')
     t_loop = time.time() - t_loop
-    if writer is not None:
-        writer.close()
+    if sink is not None:
+        sink.close()
     if stats is not None:
         stats.update(render_loop_s=t_loop, frames=n_frames, frames_per_batch=B, batches=n_batches, collectives=n_coll,
                      rerenders=n_again, world=world, rows_per_rank=r1 - r0)
-        if watching:
-            stats['watch'] = dict(watch, every=watch_every, precision=eng.precision_name)
-        if split_watching and split_watch['checks']:
-            stats['split_watch'] = dict(split_watch, every=watch_every, whole_every=whole_every, precision=eng.precision_name, split_block=eng.split_block)
-        if host_stack is not None:
-            stats['host_frames'] = host_stack          # complete: writer.close() has waited for every copy
+        if teacher is not None:
+            stats['watch'] = dict(teacher.stats(), every=watch_every, precision=eng.precision_name)
+        if student is not None and student.on and student.checks:
+            stats['split_watch'] = dict(student.stats(), every=watch_every, whole_every=student.whole_every, precision=eng.precision_name, split_block=eng.split_block)
+        if sink is not None:
+            stats['host_frames'] = sink.host_stack     # complete: sink.close() has waited for every copy
     misc = {}
     if gt_imgs is not None:
         misc.update(test_metrics(rgbs, gt_imgs.to(rgbs.device), mse_dev, ssim_dev))

@@ -45,9 +45,13 @@ class OnlineTeacherSource:
             raise R2LError(f'seed={seed} (0 .. 2^32 - 1: one word of the RandomState seed) watch_every={watch_every}')
         self.device = torch.device(getattr(engine, 'device', 'cpu'))
         self._rays_fn = rays_fn or self._launch_rays
-        self.checks, self.fallbacks = 0, []
+        from .watch import Watch
+        self._watch = Watch(len(getattr(engine, 'LADDER', (0,))), log=self.log)
         if hasattr(engine, 'set_skip_rgb0'):
             engine.set_skip_rgb0(True)        # only rgb_map is taken (as create_rand does): the coarse pass runs without its view branch
+
+    checks = property(lambda self: self._watch.checks)           # the watch's two counters
+    fallbacks = property(lambda self: self._watch.fallbacks)
 
     def draws(self, step):
         """(poses [n_pose, 3, 4] float32, focals [n_pose] float64) of a step, on the host"""
@@ -98,21 +102,19 @@ class OnlineTeacherSource:
                 return {'rgb_map': torch.empty((0, 3), dtype=torch.float32, device=ro.device)}
             return eng.render_rays(lro, lrd)
 
+        def step_down(ok, d):
+            was = getattr(eng, 'precision_name', '?')
+            now = eng.step_down()
+            what = d if not ok else 'off on the rows of another rank,'
+            line = (f'[precision] step {step}: {was} is {what} from fp16x3 on {getattr(eng, "WATCH_RAYS", "a sample")} of the batch\'s rays '
+                    f'-> {now}; batch rendered again')
+            return {'step': step, 'from': was, 'to': now, 'diffs': d}, line if rows is None or D.rank_world(group)[0] == 0 else None   # one line per run, not per rank
+
         out = render()
         if self.watch_every and step % self.watch_every == 0 and hasattr(eng, 'spot_check'):
-            for _ in range(len(getattr(eng, 'LADDER', (0,)))):
-                ok, d = eng.spot_check(lro, lrd, out) if lro.shape[0] else (True, {})
-                self.checks += 1
-                if not any_rank(not ok):
-                    break
-                was = getattr(eng, 'precision_name', '?')
-                now = eng.step_down()
-                self.fallbacks.append({'step': step, 'from': was, 'to': now, 'diffs': d})
-                out = render()
-                what = d if not ok else 'off on the rows of another rank,'
-                log = self.log if rows is None or D.rank_world(group)[0] == 0 else (lambda *a, **k: None)       # one line per run, not per rank
-                log(f'[precision] step {step}: {was} is {what} from fp16x3 on {getattr(eng, "WATCH_RAYS", "a sample")} of the batch\'s rays '
-                    f'-> {now}; batch rendered again')
+            # a rank without rows has nothing to compare, but it enters every collective and counts the check
+            out = self._watch.run(out, check=lambda got: eng.spot_check(lro, lrd, got) if lro.shape[0] else (True, {}), step_down=step_down,
+                                  again=render, agree=any_rank)
         target = out['rgb_map']
         if rows is not None:
             import torch.distributed as td

@@ -609,7 +609,7 @@ class NeRFEngine:
         return all(d[k] <= lim[k] for k in d), d
 
     def step_down(self):
-        """one rung down the ladder fp16x1 -> fp16_fp8 -> fp16x3_asm -> fp16x3 (after a failed spot_check); returns the new mode's name"""
+        """one rung down LADDER, fp16x1 -> fp16_fp8 -> fp16_mix -> fp16x3_asm -> fp16x3 (after a failed spot_check); returns the new mode's name"""
         from ._lib import PRECISIONS
         name = self.precision_name
         nxt = self.LADDER[min(self.LADDER.index(name) + 1, len(self.LADDER) - 1)] if name in self.LADDER else 'fp16x3'

@@ -665,5 +665,8 @@ def main(argv=None):
         raise SystemExit('train_teacher.py trains; render with main.py --model_name nerf --render_only --pretrained_ckpt X.tar')
     check_supported(args)
     torch.cuda.set_device(D.local_device(0))
+    if args.dist_seed >= 0:     # the one process of this trainer: numpy's and torch's generators (host and device) as dist.seed_all seeds every rank's
+        np.random.seed(args.dist_seed)
+        torch.manual_seed(args.dist_seed)
     train(args, log=lambda *a, **k: print(*a, **k, flush=True))
     return 0

@@ -555,13 +555,16 @@ def _run(cmd, cwd):
 
 def test_cli_trains_tests_saves_renders_and_resumes(pkg, tmp_path):
     """train_teacher.py with configs/lego.txt as a child process on a small scene written here; main.py --render_only on its
-    checkpoint; --resume from it.  Each child under its own timeout; a failure starts nothing further."""
+    checkpoint; --resume from it.  Each child under its own timeout; a failure starts nothing further.
+    The children train under --dist_seed 0: unseeded, about one start in eight (of seeds 0 .. 5: seed 4) draws weights whose density is zero
+    on every sample, renders white at 2 dB and does not move in 30 iterations, as the reference's own initialisation can; `hist_psnr` then
+    wanders instead of rising (2.18 -> 2.12 in the run that showed it).  With the seed the run is the same every time: 11.9 -> 20.7 dB."""
     scene = str(tmp_path / 'scene')
     write_scene(scene)
     base = ['--config', os.path.join(ROOT, 'configs', 'lego.txt'), '--datadir', scene, '--basedir', str(tmp_path), '--expname', 'cli',
             '--N_rand', '128', '--testskip', '1']
     train = ['timeout', '-k', '10', '300', sys.executable, os.path.join(ROOT, 'train_teacher.py')] + base + [
-        '--lrate', '0.002', '--precrop_iters', '10', '--i_print', '5', '--i_weights', '15', '--i_video', '100000']
+        '--lrate', '0.002', '--precrop_iters', '10', '--i_print', '5', '--i_weights', '15', '--i_video', '100000', '--dist_seed', '0']
     out = _run(train + ['--N_iters', '30', '--i_testset', '30'], str(tmp_path))
     lines = [ln for ln in out.splitlines() if ln.startswith('[TRAIN] Iter')]
     assert len(lines) == 6, out[-3000:]
