@@ -153,6 +153,9 @@ SIGNATURES = {
     'r2l_png_workspace_bytes': (C.c_longlong, [C.c_int, C.c_int, C.c_int]),
     'r2l_png_layout': (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     'r2l_png_encode': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_longlong, _vp, C.c_longlong, _vp, _vp]),
+    # PNG files read (csrc/r2l_png_decode.hip)
+    'r2l_png_decode_workspace_bytes': (C.c_longlong, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'r2l_png_decode': (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_longlong, _vp, _vp, _vp]),
     # teacher training (csrc/nerf_train.hip)
     'nerf_train_raw2outputs_backward': (C.c_int, [_vp, _vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _vp, _vp, _vp]),
     'nerf_train_batch_rays': (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _vp, C.c_double, _vp, C.c_longlong, C.c_int, C.c_float, _vp, _vp, _vp,

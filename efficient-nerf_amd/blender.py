@@ -81,6 +81,15 @@ def read_png(path):
     return out.reshape(h, w, c)
 
 
+def read_pngs(paths, decode=None):
+    """the images of `paths`, uint8 [H, W, C] each: read_png in a loop, or with decode (paths -> uint8 [n, H, W, C] on the host; --png_read_device
+    passes png.device_reader()) all of them in one call"""
+    paths = list(paths)
+    if decode is None or not paths:
+        return [read_png(p) for p in paths]
+    return list(decode(paths))
+
+
 def half_res_area(imgs):
     """cv2.resize(img, (W/2, H/2), interpolation=cv2.INTER_AREA) for an exact factor of two = the
     mean of each 2x2 block (dataset/load_blender.py:105-115).  imgs: float32 [N, H, W, C]."""
@@ -89,20 +98,19 @@ def half_res_area(imgs):
     return ((v[:, :, 0, :, 0] + v[:, :, 0, :, 1]) + (v[:, :, 1, :, 0] + v[:, :, 1, :, 1])) * np.float32(0.25)
 
 
-def load_blender_data(basedir, half_res=False, testskip=1, splits=('train', 'val', 'test')):
+def load_blender_data(basedir, half_res=False, testskip=1, splits=('train', 'val', 'test'), decode=None):
     """dataset/load_blender.py:31-120: frames[::skip] per split (skip = 1 for train or when
     testskip == 0), imgs / 255 as float32 with all channels kept, poses float32 [N,4,4],
     focal = .5 * W / tan(.5 * camera_angle_x), half_res halves H, W, focal.  Returns
-    (imgs [N,H,W,C] f32 tensor, poses [N,4,4] tensor, [H, W, focal], i_split list)."""
+    (imgs [N,H,W,C] f32 tensor, poses [N,4,4] tensor, [H, W, focal], i_split list).  decode: read_pngs', one call per split."""
     all_imgs, all_poses, counts, meta = [], [], [0], None
     for s in splits:
         with open(os.path.join(basedir, f'transforms_{s}.json')) as fp:
             meta = json.load(fp)
         skip = 1 if (s == 'train' or testskip == 0) else testskip
-        imgs, poses = [], []
-        for frame in meta['frames'][::skip]:
-            imgs.append(read_png(os.path.join(basedir, frame['file_path'] + '.png')))
-            poses.append(np.array(frame['transform_matrix']))
+        frames = meta['frames'][::skip]
+        imgs = read_pngs([os.path.join(basedir, frame['file_path'] + '.png') for frame in frames], decode)
+        poses = [np.array(frame['transform_matrix']) for frame in frames]
         imgs = (np.array(imgs) / 255.).astype(np.float32)
         counts.append(counts[-1] + imgs.shape[0])
         all_imgs.append(imgs)

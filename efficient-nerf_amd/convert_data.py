@@ -47,6 +47,7 @@ def parse_args(argv=None):
     p.add_argument('--full_res', action='store_true')
     p.add_argument('--seed', type=int, default=None, help='np.random.seed(N) in front of the two permutation draws')
     p.add_argument('--dataset_type', type=str, default='blender', choices=['blender', 'llff'])
+    p.add_argument('--png_read_device', action='store_true', help='decode the PNGs on the device (png.decode_pngs) instead of in blender.read_png')
     args = p.parse_args(argv)
     if args.dataset_type == 'llff' and (args.full_res or args.donerf):
         raise SystemExit('--full_res / --donerf belong to --dataset_type blender: LLFF images are read at factor 8 and never halved')
@@ -70,17 +71,18 @@ def kept_frames(frames, ignore):
     return [f for f in frames if f['file_path'].split('_')[-1] not in ignored]
 
 
-def load_images(datadir, splits, ignore):
-    """:124-150 with the images left as the PNGs' bytes: (uint8 [n, H0, W0, C], float32 poses [n, 4, 4], camera_angle_x)"""
+def load_images(datadir, splits, ignore, decode=None):
+    """:124-150 with the images left as the PNGs' bytes: (uint8 [n, H0, W0, C], float32 poses [n, 4, 4], camera_angle_x).  decode:
+    blender.read_pngs', one call per split"""
     metas = {}
     for s in splits:
         with open(os.path.join(datadir, f'transforms_{s}.json')) as fp:
             metas[s] = json.load(fp)
     imgs, poses = [], []
     for s in splits:
-        for frame in kept_frames(metas[s]['frames'], ignore):
-            imgs.append(blender.read_png(os.path.join(datadir, frame['file_path'] + '.png')))
-            poses.append(np.array(frame['transform_matrix']))
+        frames = kept_frames(metas[s]['frames'], ignore)
+        imgs += blender.read_pngs([os.path.join(datadir, frame['file_path'] + '.png') for frame in frames], decode)
+        poses += [np.array(frame['transform_matrix']) for frame in frames]
     if not imgs:
         raise SystemExit(f'no image left under "{datadir}" for --splits {",".join(splits)} --ignore {ignore}')
     shapes = {im.shape for im in imgs}
@@ -160,11 +162,11 @@ def llff_views(n, splits):
     return views
 
 
-def load_llff_images(datadir, splits):
+def load_llff_images(datadir, splits, decode=None):
     """:79-107 with the images left as the PNGs' bytes: (uint8 [n, H, W, 3], float32 poses [n, 3, 4], (H, W, focal))"""
     from . import llff
     try:
-        scene = llff.load_scene(datadir, factor=LLFF_FACTOR, recenter_poses=True, bd_factor=.75, spherify=False, path_zflat=False, n_pose_video=120)
+        scene = llff.load_scene(datadir, factor=LLFF_FACTOR, recenter_poses=True, bd_factor=.75, spherify=False, path_zflat=False, n_pose_video=120, decode=decode)
     except llff.LLFFError as e:
         raise SystemExit(str(e))
     views = llff_views(len(scene.poses), splits)
@@ -176,13 +178,19 @@ def load_llff_images(datadir, splits):
 def convert(args, log=print):
     """the reference's script from its arguments on; returns the paths written"""
     splits, prefix, savedir = save_layout(args)
+    decode = None
+    if getattr(args, 'png_read_device', False):
+        from . import png
+        if not torch.cuda.is_available():
+            raise SystemExit('--png_read_device: no HIP device visible to torch, and PNG decoding on the device has no CPU fallback')
+        decode = png.device_reader()
     if getattr(args, 'dataset_type', 'blender') == 'llff':
-        imgs, poses, (H, W, focal) = load_llff_images(args.datadir, splits)
+        imgs, poses, (H, W, focal) = load_llff_images(args.datadir, splits, decode)
         n_img, H0, W0, ch = imgs.shape
         log(f'Read all images and poses, done. all_imgs shape {imgs.shape}, all_poses shape {poses.shape}')
         half_res = False
     else:
-        imgs, poses, angle = load_images(args.datadir, splits, args.ignore)
+        imgs, poses, angle = load_images(args.datadir, splits, args.ignore, decode)
         n_img, H0, W0, ch = imgs.shape
         log(f'Read all images and poses, done. all_imgs shape {imgs.shape}, all_poses shape {poses.shape}')
         half_res = not args.full_res

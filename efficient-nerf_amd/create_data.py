@@ -618,9 +618,8 @@ def build_teacher_engine(args, ckpt, hwf, use_rand_focal=True, log=None, watched
     return eng
 
 
-def main(argv=None):
-    """`python create_data.py --create_data rand --config configs/lego.txt --teacher_ckpt X.tar
-    --n_pose_kd N --datadir_kd old:new` (README.md:79 of the reference)."""
+def parse_args(argv=None):
+    """(the flags of this command, the front end's): --datadir, --png_read_device and every other flag the front end knows go there"""
     import argparse
     from . import frontend as fe
     ap = argparse.ArgumentParser(add_help=False, allow_abbrev=False)      # --datadir must reach the front end, not match --datadir_kd here
@@ -633,7 +632,14 @@ def main(argv=None):
     ap.add_argument('--create_data_chunk', type=int, default=100)
     ap.add_argument('--split_size', type=int, default=4096)
     own, rest = ap.parse_known_args(argv)
-    args = fe.parse_args(rest)
+    return own, fe.parse_args(rest)
+
+
+def main(argv=None):
+    """`python create_data.py --create_data rand --config configs/lego.txt --teacher_ckpt X.tar
+    --n_pose_kd N --datadir_kd old:new` (README.md:79 of the reference)."""
+    from . import frontend as fe
+    own, args = parse_args(argv)
     if own.create_data != 'rand':
         raise SystemExit(f'--create_data {own.create_data}: only `rand` (the README pipeline) is built')
     if ':' not in own.datadir_kd or not own.teacher_ckpt:
@@ -648,7 +654,8 @@ def main(argv=None):
             raise SystemExit(f'--create_data rand on --dataset_type llff draws its poses from the scene: "{os.path.join(args.datadir, "poses_bounds.npy")}" '
                              f'is not there')
         try:
-            scene = llff.load_scene(args.datadir, args.factor, spherify=args.spherify, n_pose_video=llff.n_pose_video_from_flag(args.n_pose_video))
+            scene = llff.load_scene(args.datadir, args.factor, spherify=args.spherify, n_pose_video=llff.n_pose_video_from_flag(args.n_pose_video),
+                                    decode=fe.png_reader(args))
         except llff.LLFFError as e:
             raise SystemExit(str(e))
         H, W, focal = scene.hwf

@@ -105,7 +105,7 @@ FLAGS = [
     ('--write_video', dict(action=_BOOL)), ('--video_quality', dict(type=int, default=90)), ('--video_fps', dict(type=float, default=30)),
     # the .png files of render_path and of the student's test renders finished on the device (png.py, csrc/r2l_png.hip) instead of by
     # zlib on the host: the same pixels in other bytes; off by default
-    ('--png_device', dict(action=_BOOL)),
+    ('--png_device', dict(action=_BOOL)), ('--png_read_device', dict(action=_BOOL)),
     # auto (default): fp16_fp8 (fp16 MFMA pass + bf6 correction terms, 1.7x the speed) when the checkpoint's own activation
     # ranges, measured on every ray of the first frame and watched on every frame after it, keep it inside the 1e-4 rgb
     # contract, fp16x3_asm otherwise (R2LEngine.choose_precision / check_ranges); the teacher measures fp16x1 (its layer chain as one
@@ -302,11 +302,23 @@ def has_llff_scene(args):
     return args.dataset_type == 'llff' and args.synthetic_poses <= 0 and llff.has_scene(args.datadir)
 
 
+def png_reader(args):
+    """--png_read_device: the loaders' decode= hook (png.device_reader: the scene's PNGs inflated and unfiltered on the device, one call
+    per split), or None for blender.read_png on the host.  Without a GPU the flag is refused in one line."""
+    if not getattr(args, 'png_read_device', False):
+        return None
+    if not torch.cuda.is_available():
+        raise SystemExit('--png_read_device: no HIP device visible to torch, and PNG decoding on the device has no CPU fallback')
+    from . import png
+    return png.device_reader()
+
+
 def llff_test_views(args):
     """main.py:891-911, 1005: (scene, i_test) -- the loaded scene and its held-out views (every --llffhold-th; the loader's own
     single view nearest the average pose when --llffhold is 0)"""
     from . import llff
-    scene = llff.load_scene(args.datadir, args.factor, spherify=args.spherify, n_pose_video=llff.n_pose_video_from_flag(args.n_pose_video))
+    scene = llff.load_scene(args.datadir, args.factor, spherify=args.spherify, n_pose_video=llff.n_pose_video_from_flag(args.n_pose_video),
+                            decode=png_reader(args))
     i_test = llff.split_indices(len(scene.poses), args.llffhold)[2] if args.llffhold > 0 else np.array([scene.i_test])
     return scene, i_test
 
@@ -336,7 +348,7 @@ def load_test_set(args):
         first = json.load(fp)['frames'][0]['file_path']
     if not os.path.exists(os.path.join(args.datadir, first + '.png')):
         return load_test_poses(args) + (None,)
-    imgs, poses, hwf, _ = blender.load_blender_data(args.datadir, args.half_res, args.testskip, splits=('test',))
+    imgs, poses, hwf, _ = blender.load_blender_data(args.datadir, args.half_res, args.testskip, splits=('test',), decode=png_reader(args))
     return poses, tuple(hwf), blender.composite(imgs, args.white_bkgd)
 
 

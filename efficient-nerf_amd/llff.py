@@ -17,7 +17,7 @@ import os
 
 import numpy as np
 
-from .blender import read_png
+from .blender import read_png, read_pngs  # noqa: F401
 
 
 class LLFFError(ValueError):
@@ -138,7 +138,7 @@ def image_dir(basedir, factor):
     return os.path.join(basedir, 'images' + (f'_{factor}' if factor else ''))
 
 
-def _load_data(basedir, factor):
+def _load_data(basedir, factor, decode=None):
     """load_llff.py:68-132: (poses [3, 5, N] float64 with H, W of the first image and focal / factor, bds [2, N], bytes uint8
     [N, H, W, 3])"""
     pb = os.path.join(basedir, 'poses_bounds.npy')
@@ -158,7 +158,7 @@ def _load_data(basedir, factor):
     files = [os.path.join(imgdir, f) for f in names if f.endswith('png')]
     if poses.shape[-1] != len(files):
         raise LLFFError(f'"{imgdir}" holds {len(files)} PNG(s), "{pb}" {poses.shape[-1]} pose(s)')
-    imgs = [read_png(f)[..., :3] for f in files]
+    imgs = [im[..., :3] for im in read_pngs(files, decode)]
     shapes = {im.shape for im in imgs}
     if len(shapes) != 1 or imgs[0].shape[-1] != 3:
         raise LLFFError(f'the images under "{imgdir}" are not all of one RGB shape: {sorted(shapes)}')
@@ -186,11 +186,11 @@ class Scene:
         return int(H), int(W), float(focal)
 
 
-def load_scene(basedir, factor=8, recenter_poses=True, bd_factor=.75, spherify=False, path_zflat=False, n_pose_video=120):
-    """load_llff.py:336-456 up to its return, images left as bytes"""
+def load_scene(basedir, factor=8, recenter_poses=True, bd_factor=.75, spherify=False, path_zflat=False, n_pose_video=120, decode=None):
+    """load_llff.py:336-456 up to its return, images left as bytes.  decode: blender.read_pngs', all the images in one call"""
     if spherify:
         raise LLFFError('--spherify (360-degree LLFF captures) is not built: forward-facing scenes only')
-    poses, bds, image_bytes = _load_data(basedir, factor)
+    poses, bds, image_bytes = _load_data(basedir, factor, decode)
     # [down, right, back] -> [right, up, back]; the view index to the front
     poses = np.concatenate([poses[:, 1:2, :], -poses[:, 0:1, :], poses[:, 2:, :]], 1)
     poses = np.moveaxis(poses, -1, 0).astype(np.float32)

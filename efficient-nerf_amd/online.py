@@ -227,7 +227,7 @@ def source_from_args(args, log=print):
         if t.no_ndc:
             raise SystemExit('--kd_online on --dataset_type llff renders the NDC teacher: the teacher\'s flags ask for no_ndc, which is not built here')
         try:
-            scene = llff.load_scene(args.datadir, args.factor, spherify=args.spherify)
+            scene = llff.load_scene(args.datadir, args.factor, spherify=args.spherify, decode=fe.png_reader(args))
         except llff.LLFFError as e:           # the loader's refusals are one line each
             raise SystemExit(str(e))
         H, W, focal = scene.hwf

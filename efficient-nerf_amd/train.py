@@ -518,11 +518,12 @@ def load_test_split(args, device=None):
         return None, f'"{tf}"'
     with open(tf) as fp:
         frames = json.load(fp)['frames']
+    from .frontend import png_reader
     lost = [p for p in (os.path.join(args.datadir, f['file_path'] + '.png') for f in frames[::args.testskip or 1]) if not os.path.exists(p)]
     if lost:
         raise R2LError(f'"{tf}" names {len(lost)} image(s) that are not there, e.g. "{lost[0]}": complete the scene, or point --datadir elsewhere '
                        f'to train without test renders')
-    imgs, poses, hwf, _ = blender.load_blender_data(args.datadir, args.half_res, args.testskip, splits=('test',))
+    imgs, poses, hwf, _ = blender.load_blender_data(args.datadir, args.half_res, args.testskip, splits=('test',), decode=png_reader(args))
     gt = blender.composite(imgs, args.white_bkgd)
     return (poses, (int(hwf[0]), int(hwf[1]), float(hwf[2])), gt if device is None else gt.to(device)), None
 

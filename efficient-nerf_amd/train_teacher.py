@@ -559,8 +559,9 @@ def llff_split_and_bounds(scene, llffhold, no_ndc):
 def _blender_data(args, start, log):
     """no_batching on a Blender scene (main.py:1212-1292): one training image per step, N_rand of its pixels, the centre crop"""
     from . import blender
+    from .frontend import png_reader
     from .teacher import get_rays
-    images, poses, hwf, (i_train, i_val, i_test) = blender.load_blender_data(args.datadir, args.half_res, args.testskip)
+    images, poses, hwf, (i_train, i_val, i_test) = blender.load_blender_data(args.datadir, args.half_res, args.testskip, decode=png_reader(args))
     images = blender.composite(images, args.white_bkgd)
     H, W, focal = int(hwf[0]), int(hwf[1]), float(hwf[2])
     dev = torch.device('cuda', torch.cuda.current_device())
@@ -586,8 +587,10 @@ def _llff_data(args, log):
     """use_batching on an LLFF scene (main.py:890-919, 1137-1162, 1199-1210): random rays over all training images, no centre crop;
     NDC unless --no_ndc"""
     from . import llff
+    from .frontend import png_reader
     try:
-        scene = llff.load_scene(args.datadir, args.factor, spherify=args.spherify, n_pose_video=llff.n_pose_video_from_flag(args.n_pose_video))
+        scene = llff.load_scene(args.datadir, args.factor, spherify=args.spherify, n_pose_video=llff.n_pose_video_from_flag(args.n_pose_video),
+                                decode=png_reader(args))
     except llff.LLFFError as e:
         raise SystemExit(str(e))
     H, W, focal = scene.hwf                                   # main.py:898: of poses[0]

@@ -641,6 +641,38 @@ int r2l_png_layout(int H, int W, int* rows_per_segment, int* n_segments);
 int r2l_png_encode(const float* rgb_dev, int n_img, int H, int W, int filter, void* workspace_dev, long long workspace_bytes,
                    unsigned char* out_dev, long long pitch, long long* sizes_dev, void* stream);
 
+/* ---- PNG files read (csrc/png_inflate.h, csrc/r2l_png_decode.hip; host side: png.decode_pngs) ----
+ * n_img zlib streams (the concatenated IDAT payloads of 8-bit, non-interlaced files of one shape, C = 1, 2, 3 or 4 bytes per pixel) become
+ * pixels: stream k is zstreams_dev[offsets_dev[k] .. offsets_dev[k + 1]), its picture out_dev[k] of uint8 [n_img, H, W, C].  One
+ * workgroup of one wave per stream inflates it (stored, fixed and dynamic blocks, the Adler-32 verified) into the workspace through a
+ * 64 KiB window in LDS; a second launch undoes the five row filters, 64 rows at a time on a skewed wavefront.  Every read of a stream is
+ * checked against its end and every write against H (W C + 1) bytes: whatever is wrong with stream k comes back as status_dev[k], an
+ * r2l_png_status; such a picture is unspecified (and in bounds) and the others are not disturbed.  Nothing is allocated or copied
+ * and the host does not wait; no atomics: the same streams give the same bytes, and a picture does not depend on the other streams.
+ * H and W from 1 to 16384, n_img up to 65535, offsets_dev 8-byte, status_dev 4-byte, workspace_dev 16-byte aligned, a workspace of
+ * r2l_png_decode_workspace_bytes (a negative code on a bad argument; host only): R2L_EINVAL otherwise, before a device is touched.
+ * n_img = 0 is a no-op.  The offsets are trusted as the pointers are: ascending, a stream shorter than 2 GiB. */
+enum r2l_png_status {
+    R2L_PNG_OK = 0,
+    R2L_PNG_TRUNCATED = 1,      /* the stream ends inside a header, a block or the Adler-32 */
+    R2L_PNG_BAD_HEADER = 2,     /* not a zlib header: method, window, check bits, or a preset dictionary */
+    R2L_PNG_BAD_BLOCK = 3,      /* block type 3 */
+    R2L_PNG_BAD_STORED = 4,     /* a stored block whose NLEN is not the complement of LEN */
+    R2L_PNG_OVERSUBSCRIBED = 5, /* code lengths that claim more codes than there are */
+    R2L_PNG_INCOMPLETE = 6,     /* code lengths that leave codes unused (other than a single code of one bit) */
+    R2L_PNG_BAD_LENGTHS = 7,    /* too many lengths, a repeat with nothing to repeat or past the end, no end-of-block code */
+    R2L_PNG_BAD_CODE = 8,       /* bits that are no symbol of the code, or a symbol deflate does not define */
+    R2L_PNG_FAR_DISTANCE = 9,   /* a match that starts before the first byte of the output */
+    R2L_PNG_TOO_LONG = 10,      /* more bytes than the image needs */
+    R2L_PNG_TOO_SHORT = 11,     /* fewer */
+    R2L_PNG_BAD_FILTER = 12,    /* a row whose filter byte is above 4 */
+    R2L_PNG_BAD_ADLER = 13,     /* the Adler-32 of the bytes is not the stream's */
+    R2L_PNG_BAD_OFFSETS = 14    /* offsets that do not ascend, or a stream of 2 GiB or more */
+};
+long long r2l_png_decode_workspace_bytes(int n_img, int H, int W, int C);
+int r2l_png_decode(const unsigned char* zstreams_dev, const long long* offsets_dev, int n_img, int H, int W, int C, void* workspace_dev,
+                   long long workspace_bytes, unsigned char* out_dev, int* status_dev, void* stream);
+
 /* ---- training of the NeRF teacher (csrc/nerf_train.hip; host mirror: efficient-nerf_amd/train_teacher.py) ----
  * A teacher step is the launches above (layers, embedding, scans, loss, Adam) plus the backward pass of nerf_raw2outputs[_noise]:
  * g_raw_dev [n,S,4] from g_rgb_map_dev [n,3], the only output the losses reach (main.py:728 detaches z_samples).  raw [n,S,4],
