@@ -4,7 +4,9 @@ The files are written here with zlib and struct (tests/png_decode_cases.py); the
 stream before the device sees it, blender.read_png, and the pictures the files were made from; every comparison is array_equal.  The
 unfilter kernel walks bands of 64 rows in tiles of 64 steps: heights 63, 64, 65 and 129 and widths 63, 64 and 65 lie around both.  The
 broken streams have all been through the same text on the CPU under the sanitizers (test_png_decode_cpu.py); here they are tests of a
-refusal by bounds-checked code."""
+refusal by bounds-checked code.  The streams laid out on purpose (codes of up to 15 bits and every length and distance symbol, matches
+around every turn of the ring and the longest flushes, streams that end around a fetch of 8 KiB, the refusals png_inflate.h promises,
+600 files in one call) go through decode_pngs and through the C-ABI call, and a refusal has to be the one status the CPU run gave."""
 import ctypes as C
 import os
 import shutil
@@ -204,6 +206,106 @@ def test_broken_files_are_refused_by_name_and_disturb_nothing(pkg, built_lib, tm
         with pytest.raises(ValueError) as ours:
             png.decode_pngs([ok, path])
         assert str(ours.value) == str(host.value) and path in str(ours.value), name
+
+
+# ---- streams laid out on purpose (tests/png_decode_cases.py; what they reach is asserted in test_png_decode_cpu.py) ----
+def status_codes():
+    from efficient_nerf_amd import png
+    assert sorted(png.DECODE_STATUS) == list(range(1, len(K.STATUS_WORDS)))
+    return {word: k for k, word in enumerate(K.STATUS_WORDS)}
+
+
+def is_picture_of(px, raw, W, ch):
+    """px [H, W, ch] is what the filtered bytes `raw` reconstruct to"""
+    return refiltered(px, np.frombuffer(raw, np.uint8)[::W * ch + 1]) == raw
+
+
+def between_good(good, bad):
+    """good[0], bad[0], good[1], bad[1], ..., good again: every broken stream between two good ones"""
+    streams = []
+    for k, s in enumerate(bad):
+        streams += [good[k % len(good)], s]
+    return streams + [good[len(bad) % len(good)]]
+
+
+def test_long_codes_ring_turns_and_mixed_blocks(pkg, built_lib):
+    built = K.built_streams()
+    assert sorted(built) == ['long-codes', 'mixed-blocks', 'ring-0', 'ring-1', 'ring-2', 'ring-3']
+    for shape in (K.HAND, K.RING):
+        names = [name for name, b in built.items() if b[:3] == shape]
+        H, W, ch = shape
+        for name in names:
+            assert zlib.decompress(built[name][3]) == built[name][4] and len(built[name][4]) == H * (W * ch + 1), name      # zlib first
+        files = decode([K.png_file(H, W, ch, built[name][3], idat_bytes=8192 if k % 2 else None) for k, name in enumerate(names)])
+        abi, status = decode_streams([built[name][3] for name in names], H, W, ch)
+        assert status == [0] * len(names), status
+        for k, name in enumerate(names):
+            assert is_picture_of(files[k], built[name][4], W, ch), name
+            assert np.array_equal(abi[k], files[k]), name
+
+
+def test_streams_that_end_around_a_fetch_and_refusals_behind_the_first(pkg, built_lib):
+    from efficient_nerf_amd import png
+    good, bad = K.refill_streams()
+    code = status_codes()
+    H, W, ch = K.REFILL
+    totals = sorted(good)
+    assert totals == [K.PNG_INW_BYTES * k + r for k in (1, 2) for r in range(-4, 6)] and len(bad) == 8
+    for total in totals:
+        assert zlib.decompress(good[total][0]) == good[total][1] and len(good[total][0]) == total
+    files = decode([K.png_file(H, W, ch, good[total][0]) for total in totals])
+    for k, total in enumerate(totals):
+        assert is_picture_of(files[k], good[total][1], W, ch), total
+    streams = between_good([good[total][0] for total in totals], [s for s, _ in bad.values()])
+    abi, status = decode_streams(streams, H, W, ch)
+    assert status[1::2] == [code[word] for _, word in bad.values()], status
+    assert status[0::2] == [0] * (len(bad) + 1), status
+    for k in range(0, len(streams), 2):
+        assert np.array_equal(abi[k], files[k // 2 % len(totals)]), k
+    for name, (stream, word) in bad.items():
+        with pytest.raises(ValueError) as e:
+            png.decode_pngs([K.png_file(H, W, ch, good[totals[0]][0]), K.png_file(H, W, ch, stream)])
+        assert str(e.value) == f'<bytes #1>: {png.DECODE_STATUS[code[word]]}', (name, str(e.value))
+
+
+def test_promised_refusals_give_their_status(pkg, built_lib):
+    from efficient_nerf_amd import png
+    promised, good, raw = K.promised_streams()
+    code = status_codes()
+    H, W, ch = K.SMALL
+    assert zlib.decompress(good) == raw and sorted(promised) == sorted(K.PROMISED) and len(promised) == 29
+    want = decode([K.png_file(H, W, ch, good)])[0]
+    assert is_picture_of(want, raw, W, ch)
+    streams = between_good([good], list(promised.values()))
+    abi, status = decode_streams(streams, H, W, ch)
+    assert status[1::2] == [code[K.PROMISED[name]] for name in promised], list(zip(promised, status[1::2]))
+    assert status[0::2] == [0] * (len(promised) + 1), status
+    for k, st in enumerate(status):
+        if st == 0:
+            assert np.array_equal(abi[k], want), k
+    # through decode_pngs: the refusal in the status' words, and the streams that pass
+    ok = K.png_file(H, W, ch, good)
+    for name, stream in promised.items():
+        if K.PROMISED[name] == 'OK':
+            assert np.array_equal(decode([ok, K.png_file(H, W, ch, stream), ok]), np.stack([want] * 3)), name
+        else:
+            with pytest.raises(ValueError) as e:
+                png.decode_pngs([ok, K.png_file(H, W, ch, stream), ok])
+            assert str(e.value) == f'<bytes #1>: {png.DECODE_STATUS[code[K.PROMISED[name]]]}', (name, str(e.value))
+
+
+def test_more_workgroups_than_run_at_once(pkg, built_lib):
+    card = K.card_streams()
+    code = status_codes()
+    H, W, ch = K.CARD
+    assert len(card) == 600
+    pictures = np.stack([img for _, img, _, _ in card])
+    assert np.array_equal(decode([K.png_file(H, W, ch, good) for good, _, _, _ in card]), pictures)
+    abi, status = decode_streams([broken or good for good, _, broken, _ in card], H, W, ch)
+    assert status == [code[word] if broken else 0 for _, _, broken, word in card]
+    assert sum(st != 0 for st in status) == 86
+    keep = np.array(status) == 0
+    assert np.array_equal(abi[keep], pictures[keep])
 
 
 # ---- the loaders ----
